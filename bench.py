@@ -2,9 +2,21 @@
 clips/sec of forward + backward + clip_grad_norm_(1.0) + AdamW over 16×224² video + 200×6 IMU clips,
 batch 32 per GPU, VideoMAE-B video backbone (the reference default), bf16 MFMA compute.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: set up, W warm-up steps, K timed steps, the JSON
+line (`value` = clips/s over the timed region, `ms_per_step` = the milliseconds one timed step took).  `--full` adds
+the measurements that take runs or launches of their own: the traced warm-up step (`kernels`: per-kernel-family
+breakdown) and the dominant kernel's HIP-event roofline with its PMC traffic / MFMA utilisation, the on-box MFMA peak
+probe, and the CPU-oracle baseline (`cpu_baseline`); `--no-trace` / `--no-cpu-baseline` switch single ones of those
+off again.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32; see
+`dump_outputs`) from the same path the plain run times; weights and inputs are seeded, so two builds run with the same
+arguments compare output for output.  The outputs themselves repeat to the bit only over short runs: with the default
+GEMM routing (`gemm_routing` in the JSON line) a long training run can differ from another by more than rounding
+after some dozens of steps; `CMHAR_BLASLT=""` in the environment (hand-written kernels only) is the setting for
+bit-exact comparisons.
 
 One step = the body of CrossModalTrainer.train_epoch (src/train/trainer.py:130-144) on synthetic inputs already
 resident in HBM: model(imu, video) → SigmoidContrastiveLoss → zero_grad → backward (+ RCCL gradient all-reduce
@@ -22,9 +34,10 @@ is over the gathered global batch (DataParallel semantics).  Rank 0 prints one J
   imu       config 1 on the HIP path (the reference runs it on the CPU): IMU-only classifier (IMUEncoder + the
             256-128 MLP head, models.py:296-348) fine-tune step of ClassificationTrainer (CE, clip 1.0, AdamW over
             encoder + head), 6x200 windows, batch 8; `clips/sec` = windows/s.  Its CPU counterpart is the headline
-            line's `cpu_baseline.imu_only_b8_train_windows_per_sec`.
-For the non-headline workloads `roofline` is the whole step's algorithmic FLOP rate against the bf16 / fp16 peak
-(`kernel`: "whole step"); the headline's is the dominant single kernel's (HIP events) with PMC traffic.
+            `--full` line's `cpu_baseline.imu_only_b8_train_windows_per_sec`.
+For the non-headline workloads, and the headline without `--full`, `roofline` is the whole step's algorithmic FLOP
+rate against the bf16 / fp16 peak (`kernel`: "whole step"); the headline's under `--full` is the dominant single
+kernel's (HIP events) with PMC traffic.
 """
 import argparse
 import json
@@ -123,8 +136,14 @@ def _videomae_overlap():
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=50)     # >= 50 timed steps after >= 10 warm-up
+    # timed steps; default 50 (>= 50 timed steps after >= 10 warm-up), 313 for ood_fp16
+    ap.add_argument('--steps', type=int, default=None)
     ap.add_argument('--warmup', type=int, default=10)
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: traced warm-up step and dominant-kernel '
+                         'roofline, MFMA peak probe, CPU-oracle baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB in all)')
     ap.add_argument('--workload', default='videomae', choices=sorted(WORKLOADS))
     ap.add_argument('--batch', type=int, default=None)
     ap.add_argument('--frames', type=int, default=None)
@@ -144,8 +163,10 @@ def parse():
     for k, v in WORKLOADS[args.workload].items():
         if getattr(args, k) is None:
             setattr(args, k, v)
-    if args.workload == 'ood_fp16' and '--steps' not in sys.argv:
-        args.steps = 313                 # BASELINE config 5: a 10k-clip stream (313 batches of 32)
+    if args.steps is None:               # BASELINE config 5: a 10k-clip stream (313 batches of 32)
+        args.steps = 313 if args.workload == 'ood_fp16' else 50
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     return args
 
 
@@ -374,7 +395,11 @@ def r3d_flops(m, B, T, H, W):
 
 class Workload:
     """One benchmark configuration: `step()` runs one step on this rank's resident batch; `flops_per_clip` is the
-    step's algorithmic FLOPs per clip (the whole-step roofline numerator)."""
+    step's algorithmic FLOPs per clip (the whole-step roofline numerator); `last` names the device tensors the
+    latest step handed back besides its return value (references only: nothing is copied or synchronised), `returns`
+    what that return value is."""
+    last = {}
+    returns = 'loss'
 
 
 def imu_flops_per_window(T, d=128, layers=4, ff=512, patch=16, hidden=(256, 128), classes=32):
@@ -404,7 +429,9 @@ def _imu_workload(args, W, dev, rank, world):
     labels = torch.randint(0, cfg.model.num_classes, (B,), device=dev, generator=g)
 
     def step():
-        return tr.train_step(imu, labels)[1]
+        logits, loss = tr.train_step(imu, labels)
+        W.last = {'logits': logits}
+        return loss
     W.model, W.B, W.step, W.training = model, B, step, True
     W.flops_per_clip = 3 * imu_flops_per_window(args.imu_len, ff=4 * cfg.model.imu_d_model,
                                                 hidden=tuple(cfg.model.classifier_hidden_dims),
@@ -467,8 +494,9 @@ def build_workload(args, dev, rank, world):
                 a, b = model(imu, video)
                 K.gemm(0, a, b, S, bias=bias, alpha=10.0)       # SigLIP logits exp(log 10)·a·bᵀ + bias
                 pred, energy, _ = logits_energy(S)
+            W.last = {'imu_embeddings': a, 'video_embeddings': b, 'logits': S, 'pred': pred}
             return energy
-        W.step, W.flops_per_clip = step, fwd_f
+        W.step, W.flops_per_clip, W.returns = step, fwd_f, 'energy'
         W.metric = 'clips/sec OOD energy-score eval stream, fp16 inference, 16x224^2 video + 200x6 IMU, batch 32'
         W.workload = (f'OOD eval stream (BASELINE config 5): CrossModalModel eval forward, VideoMAE-B {args.frames}x'
                       f'{args.image}^2 + IMU 6x{args.imu_len}, SigLIP logits, energy score; ring of 8 distinct batches')
@@ -498,7 +526,9 @@ def build_workload(args, dev, rank, world):
         def loss_of():
             # global-batch mean CE under data parallelism (equal shards): the SUM all-reduce of the gradients of
             # mean/world gives the gradient of DataParallel's gathered mean
-            loss = cross_entropy(model(imu, video), labels)
+            logits = model(imu, video)
+            W.last = {'logits': logits}
+            loss = cross_entropy(logits, labels)
             return loss * (1.0 / world) if world > 1 else loss
         Lk = (args.frames // 2) * (args.image // 16) ** 2
         Lq = 1 + (args.imu_len - 16) // 16 + 1
@@ -513,6 +543,7 @@ def build_workload(args, dev, rank, world):
 
         def loss_of():
             a, b = model(imu, video)
+            W.last = {'imu_embeddings': a, 'video_embeddings': b}
             return loss_fn(a, b)
         if args.workload == 'r3d':
             fwd_r, stem = r3d_flops(backbone, B, args.frames, args.image, args.image)
@@ -541,6 +572,44 @@ def build_workload(args, dev, rank, world):
     return W
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+DUMP_SAMPLE = 1 << 21          # elements of the parameter / gradient samples (8 MiB each as float32)
+
+
+def dump_outputs(path, W, result):
+    """What a caller of the timed step holds after its last call, as `path`/<name>.npy in float32: the step's return
+    value (`loss`, or `energy` for ood_fp16), the model outputs it was computed from (`W.last`: embeddings / logits /
+    predictions), and — for the training workloads, whose step also updates the model in place — `param_sample` and
+    `grad_sample`: the same seeded sample of every parameter after the optimizer step and of its gradient
+    (DUMP_SAMPLE elements in all, shared out by size, at least one per tensor, in named_parameters() order)."""
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = {W.returns: result, **W.last}
+    if W.training:
+        named = [(n, p) for n, p in W.model.named_parameters() if p.requires_grad]
+        total = sum(p.numel() for _, p in named)
+        g = torch.Generator().manual_seed(20240)
+        ps, gs = [], []
+        for _, p in named:
+            k = min(p.numel(), max(1, DUMP_SAMPLE * p.numel() // total))
+            idx = torch.randint(0, p.numel(), (k,), generator=g).to(p.device)
+            ps.append(p.detach().reshape(-1)[idx].float())
+            if p.grad is not None:
+                gs.append(p.grad.detach().reshape(-1)[idx].float())
+            else:
+                gs.append(torch.zeros(k, device=p.device))
+        arrays['param_sample'], arrays['grad_sample'] = torch.cat(ps), torch.cat(gs)
+    os.makedirs(path, exist_ok=True)
+    size = 0
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().float().cpu().numpy())
+        size += a.nbytes
+        if size > DUMP_LIMIT_BYTES:
+            raise RuntimeError(f'--dump-outputs: more than {DUMP_LIMIT_BYTES} bytes at {name}')
+        np.save(os.path.join(path, name + '.npy'), a)
+    log(f'wrote {len(arrays)} arrays ({size} bytes) to {path}')
+
+
 def main():
     args = parse()
     from cmhar import dist as cdist
@@ -559,10 +628,10 @@ def main():
     W = build_workload(args, dev, rank, world)
     step, B = W.step, W.B
     headline = args.workload == 'videomae'
-    trace = headline and not args.no_trace
+    trace = headline and args.full and not args.no_trace
 
-    # Warm-up; its last step runs with every GEMM / attention launch bracketed by HIP events, which gives the
-    # per-kernel-family breakdown and picks the dominant single kernel.  The timed loop then brackets ONLY that
+    # Warm-up; under --full its last step runs with every GEMM / attention launch bracketed by HIP events, which gives
+    # the per-kernel-family breakdown and picks the dominant single kernel.  The timed loop then brackets ONLY that
     # kernel's launches (the events of all ~180 traced launches cost ~1.5 ms/step of stream bubbles).
     # The traced warm-up step runs the backward's weight gradients on the main stream (overlap_wgrad off): its
     # per-kernel times are then each kernel alone on the chip, not shares of two concurrent streams.
@@ -604,6 +673,9 @@ def main():
     if rank == 0:
         log(f'timed region: {elapsed:.3f} s')
     K.TRACE.active = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, W, loss)
+    last_result = float(loss.float().mean().item())      # the last timed step's return value (mean of `energy`)
     last_losses = None
     if world > 1:
         dist.barrier()
@@ -630,7 +702,7 @@ def main():
     roof = None
     peak_meas = None
     peak_shapes = {}
-    if headline and rank == 0 and os.environ.get('CMHAR_BENCH_PEAK_PROBE', '1') == '1':
+    if headline and args.full and rank == 0 and os.environ.get('CMHAR_BENCH_PEAK_PROBE', '1') == '1':
         peak_meas = measure_mfma_peak(dev, per_shape=peak_shapes)   # after the timed region: no perturbation
         log(f'on-box MFMA peak probe: {peak_meas:.1f} TFLOP/s')
     summ = K.TRACE.summary() if trace else {}
@@ -663,7 +735,7 @@ def main():
         mf = mfma_util(name, args.mfma_json)
         if mf is not None:
             roof['mfma_util'] = mf
-    elif not headline:
+    elif not (headline and args.full):
         roof = {'bound': 'mfma', 'achieved': round(whole_tflops, 1), 'peak': peak, 'unit': 'TFLOP/s',
                 'frac': round(whole_tflops / peak, 4), 'traffic': None, 'kernel': 'whole step (all kernels)'}
 
@@ -680,9 +752,12 @@ def main():
            'executed_gflop_per_clip': round(exec_flops / 1e9, 2),
            'reference_algorithmic_gflop_per_clip': round(W.flops_per_clip / 1e9, 2),
            'first_warmup_loss': first_loss,
+           'last_' + W.returns: last_result,
+           # the bf16 / fp16 forward-layout "N,K" shapes that go to hipBLASLt instead of the hand-written kernels
+           'gemm_routing': {'hipblaslt_shapes': sorted(f'{n},{k}' for n, k in K._BLASLT)},
            'last_loss_per_rank': last_losses,
            'max_mem_gb': round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and headline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and headline:
         out['cpu_baseline'] = cpu_baseline(W.make_cfg, args.cpu_batch, args.cpu_warmup, args.cpu_steps, args.frames,
                                            args.image, args.imu_len)
     if rank == 0:

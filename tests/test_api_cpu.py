@@ -3,6 +3,7 @@ have the reference's constructor signatures, attributes and EXACT state_dict key
 key lists recorded from the reference in the golden fixtures); config field parity."""
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
@@ -272,3 +273,20 @@ def test_bench_imu_flops_count():
     want = 2 * 12 * 16 * d + 4 * (2 * n * (4 * d * d + 2 * d * ff) + 4 * n * n * d) + \
         2 * (128 * 256 + 256 * 128 + 128 * 32)
     assert bench.imu_flops_per_window(200) == want
+
+
+def test_bench_arguments(monkeypatch):
+    """bench.parse: `--steps` sets the number of timed steps in either spelling, for every workload (defaults: 50,
+    and the 313-batch stream of ood_fp16); `--full` is off unless given; `--dump-outputs` takes the directory."""
+    import bench
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, 'argv', ['bench.py', *argv])
+        return bench.parse()
+    a = parse('--gpus', '1', '--steps', '7', '--warmup', '2')
+    assert (a.steps, a.warmup, a.full, a.dump_outputs, a.workload) == (7, 2, False, None, 'videomae')
+    assert parse().steps == 50 and parse('--workload', 'ood_fp16').steps == 313
+    assert parse('--workload', 'ood_fp16', '--steps=5').steps == 5
+    assert parse('--workload', 'ood_fp16', '--steps', '5').steps == 5
+    a = parse('--full', '--dump-outputs', 'some/dir')
+    assert a.full and a.dump_outputs == 'some/dir' and not a.no_trace and not a.no_cpu_baseline

@@ -199,3 +199,115 @@ def test_bench_imu_workload(tmp_path):
     assert rec['config']['per_gpu_batch'] == 8 and rec['dtype'] == 'fp32' and rec['n_gpus'] == 1
     assert rec['value'] > 0 and abs(rec['value'] - 8 * 1000 / rec['ms_per_step']) <= 1e-3 * rec['value']
     assert math.isfinite(rec['first_warmup_loss'])
+
+
+def _bench_dumps(tmp_path, runs, *args):
+    """`runs` plain bench.py processes with the same arguments, started together, each with its own --dump-outputs
+    directory: [(JSON record, {name: array})].  Every dump is float32, finite and at most 64 MB in all."""
+    import numpy as np
+    procs = [subprocess.Popen([sys.executable, '-u', os.path.join(REPO, 'bench.py'), '--gpus', '1', *args,
+                               '--dump-outputs', str(tmp_path / f'dump{i}')],
+                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=str(tmp_path)) for i in range(runs)]
+    outs = []
+    for p in procs:
+        try:
+            out, err = p.communicate(timeout=240)
+        except subprocess.TimeoutExpired:
+            for q in procs:
+                q.kill()
+            raise
+        outs.append((p.returncode, out.decode(errors='replace'), err.decode(errors='replace')))
+    res = []
+    for i, (rc, out, err) in enumerate(outs):
+        assert rc == 0, err[-3000:]
+        lines = [ln for ln in out.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        assert 'kernels' not in rec and 'cpu_baseline' not in rec      # a plain run: nothing of --full
+        arrs = {f.stem: np.load(f) for f in (tmp_path / f'dump{i}').iterdir()}
+        assert all(f.suffix == '.npy' for f in (tmp_path / f'dump{i}').iterdir())
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2 ** 20
+        res.append((rec, arrs))
+    return res
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR` on the small fp32 IMU workload (a plain run without `--full`): after the timed
+    steps DIR holds what the last step computed — its return value (`loss`, the `last_loss` of the JSON line), the
+    logits it came from (the loss is their cross-entropy against labels the test does not see, so only its range is
+    checked: 0 < loss, and below log(classes) + max |logit| spread), and the seeded samples of the updated parameters
+    and their gradients.  Two runs with the same arguments (started together) see the same weights and inputs and run
+    the same kernels, none of which accumulates with atomics; all four arrays must agree to fp32 summation order
+    (1e-4 relative + 1e-5 absolute: ~100x fp32 epsilon per summed term of the 128-wide rows; a changed input or
+    weight moves logits and gradients by O(their size)).  `steps` and `ms_per_step` describe the timed region."""
+    import numpy as np
+    res = _bench_dumps(tmp_path, 2, '--workload', 'imu', '--steps', '2', '--warmup', '1')
+    for rec, arrs in res:
+        assert rec['steps'] == 2 and rec['warmup'] == 1 and rec['ms_per_step'] > 0
+        assert abs(rec['value'] - 8 * 1000 / rec['ms_per_step']) <= 1e-3 * rec['value']
+        assert sorted(arrs) == ['grad_sample', 'logits', 'loss', 'param_sample']
+        lg = arrs['logits']
+        assert lg.shape[0] == 8 and lg.ndim == 2 and arrs['loss'].size == 1
+        assert float(arrs['loss'].reshape(-1)[0]) == pytest.approx(rec['last_loss'], rel=1e-6)
+        assert 0 < rec['last_loss'] <= math.log(lg.shape[1]) + float(lg.max() - lg.min())
+        assert arrs['param_sample'].shape == arrs['grad_sample'].shape and arrs['param_sample'].size > 1000
+        assert np.abs(arrs['grad_sample']).max() > 0 and np.abs(lg).max() > 0
+    for name in ('logits', 'loss', 'param_sample', 'grad_sample'):
+        np.testing.assert_allclose(res[0][1][name], res[1][1][name], rtol=1e-4, atol=1e-5, err_msg=name)
+
+
+# the VideoMAE-B workloads at a small clip (4 frames of 64 x 64: 32 tokens per clip), 8 clips
+SMALL_CLIP = ('--batch', '8', '--frames', '4', '--image', '64', '--steps', '2', '--warmup', '1')
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_headline(tmp_path):
+    """The headline bf16 training workload's dump: `imu_embeddings` / `video_embeddings` are the model outputs of the
+    last timed step — unit rows (l2_normalize; the video rows are bf16 values, 2^-8 per element, bound 1e-2 on the
+    norm) — and `loss` (= `last_loss` of the JSON line) is the SigLIP loss of exactly those arrays: the oracle's
+    loss at the initial temperature log 10 and bias -10 matches within 5e-4 (the two AdamW steps before the last
+    forward move either scalar by at most lr = 1e-5 each, i.e. every logit by <= 2.2e-4, and the mean-reduced loss
+    by no more; fp32 rounding of a loss <= 10 is 1e-5)."""
+    import numpy as np
+    import torch
+    from oracle import cpu_model as O
+    (rec, arrs), = _bench_dumps(tmp_path, 1, *SMALL_CLIP)
+    assert sorted(arrs) == ['grad_sample', 'imu_embeddings', 'loss', 'param_sample', 'video_embeddings']
+    a, b = arrs['imu_embeddings'], arrs['video_embeddings']
+    assert a.shape == b.shape == (8, 256) and rec['dtype'] == 'bf16' and rec['config']['per_gpu_batch'] == 8
+    np.testing.assert_allclose(np.linalg.norm(a, axis=1), 1.0, atol=1e-4)
+    np.testing.assert_allclose(np.linalg.norm(b, axis=1), 1.0, atol=1e-2)
+    loss = float(arrs['loss'].reshape(-1)[0])
+    assert loss == pytest.approx(rec['last_loss'], rel=1e-6)
+    want = float(O.siglip_loss(torch.from_numpy(a), torch.from_numpy(b), torch.tensor(math.log(10.0)),
+                               torch.tensor(-10.0)))
+    assert abs(loss - want) <= 5e-4, (loss, want)
+    assert arrs['param_sample'].shape == arrs['grad_sample'].shape and np.abs(arrs['grad_sample']).max() > 0
+    # the line names the GEMM routing in use ("N,K" shapes on hipBLASLt; the default list unless CMHAR_BLASLT is set)
+    shapes = rec['gemm_routing']['hipblaslt_shapes']
+    assert isinstance(shapes, list) and all(len(s.split(',')) == 2 for s in shapes)
+    if 'CMHAR_BLASLT' not in os.environ:
+        assert '768,768' in shapes
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_ood_fp16(tmp_path):
+    """The fp16 OOD stream's dump is self-consistent: `logits` = 10 a b^T - 10 of the dumped embeddings (fp16 values,
+    fp32 accumulation over 256 products of unit rows: 1e-3 absolute on logits within [-20, 0]), `pred` their row
+    argmax, `energy` = -logsumexp of the rows (fp32, 1e-4), `last_energy` of the JSON line its mean; unit rows to
+    fp16 precision (2^-11 per element, bound 5e-3 on the norm).  No parameter samples: nothing is trained."""
+    import numpy as np
+    (rec, arrs), = _bench_dumps(tmp_path, 1, '--workload', 'ood_fp16', *SMALL_CLIP)
+    assert sorted(arrs) == ['energy', 'imu_embeddings', 'logits', 'pred', 'video_embeddings']
+    a, b, lg = arrs['imu_embeddings'].astype(np.float64), arrs['video_embeddings'].astype(np.float64), arrs['logits']
+    assert a.shape == b.shape == (8, 256) and lg.shape == (8, 8) and rec['dtype'] == 'fp16' and rec['steps'] == 2
+    np.testing.assert_allclose(np.linalg.norm(a, axis=1), 1.0, atol=5e-3)
+    np.testing.assert_allclose(np.linalg.norm(b, axis=1), 1.0, atol=5e-3)
+    np.testing.assert_allclose(lg, 10.0 * a @ b.T - 10.0, atol=1e-3)
+    assert (arrs['pred'] == lg.argmax(axis=1)).all()
+    m = lg.astype(np.float64).max(axis=1)
+    want = -(m + np.log(np.exp(lg - m[:, None]).sum(axis=1)))
+    np.testing.assert_allclose(arrs['energy'], want, atol=1e-4)
+    assert float(arrs['energy'].mean()) == pytest.approx(rec['last_energy'], rel=1e-5)

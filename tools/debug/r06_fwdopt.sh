@@ -15,7 +15,7 @@ timeout -k 10 300 python -u tools/debug/attn_ab.py var/base.so crossmodal-imu-vi
 grep -v amdgpu.ids gpurun_out/r06o_attn_ab.log
 for rep in 1 2; do
   for opt in 0 1; do
-    CMHAR_ATTN_FWD_OPT=$opt timeout -k 10 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline \
+    CMHAR_ATTN_FWD_OPT=$opt timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline \
       > gpurun_out/r06o_step_${opt}_${rep}.log 2>&1 || exit $?
     echo "fwd_opt=$opt rep=$rep $(tail -1 gpurun_out/r06o_step_${opt}_${rep}.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); k=d["kernels"]; print(d["value"], d["ms_per_step"], k["attn_fwd_bf16"])')"
   done

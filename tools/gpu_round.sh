@@ -2,6 +2,7 @@
 # One GPU session: parity tests, smoke, bench, optional rocprofv3 kernel-trace summary of a short bench.
 # Stops at the first crash-like exit status (anything other than 0 / 1).
 # usage: tools/gpu_round.sh TAG [--tests] [--smoke] [--bench "args"] [--prof "args"]
+# (bench args: "--full" for the kernel breakdown, dominant-kernel roofline and CPU baseline beside the headline figure)
 TAG=$1; shift
 mkdir -p gpurun_out
 export TMPDIR=/tmp
