@@ -225,6 +225,21 @@ int cmhar_copy2d(int in_dtype, int out_dtype, int rows, int cols, const void* sr
 int cmhar_logits_energy(int dtype, int N, int C, const void* logits, long ld, float temperature, int* pred,
                         float* energy, float* maxlogit, hipStream_t stream);
 
+/* Fused similarity top-k (no reference counterpart: deep k-NN OOD scores, Sun et al. 2022, and cross-modal
+ * retrieval recall@k).  s[i][j] = Σ_c q[i][c]·bank[j][c] accumulated in fp32 (q: [nq, d] rows of stride ldq, bank:
+ * [nb, d] rows of stride ldb, both `dtype`, strides in elements); vals / idx [nq, k] row-major get each query's k
+ * largest scores, descending, EQUAL SCORES BY ASCENDING BANK INDEX, so the result is a pure function of the inputs.
+ * self_offset >= 0 leaves bank row self_offset + i out of query i's candidates (leave-one-out scoring of a bank, or
+ * of a slice of it, against itself); -1 leaves nothing out.  The nq x nb scores are never stored.  Inputs are
+ * assumed finite.  Supported: 32 <= d <= 1024 with d % 32 == 0, 1 <= k <= 64, k <= nb - (self_offset >= 0), nq >= 1,
+ * 16-byte aligned rows (pointers; ld % 8 == 0 for 16-bit, ld % 4 == 0 for fp32); anything else returns
+ * hipErrorInvalidValue and launches nothing.  ws: cmhar_sim_topk_ws(nq, nb, k) BYTES (0 when the launch uses one
+ * bank range); cmhar_sim_topk_splits is the number of bank ranges the launch walks in parallel (plan query). */
+long cmhar_sim_topk_ws(int nq, int nb, int k);
+int cmhar_sim_topk_splits(int nq, int nb, int k);
+int cmhar_sim_topk(int dtype, int nq, int nb, int d, int k, const void* q, long ldq, const void* bank, long ldb,
+                   long self_offset, float* vals, int* idx, void* ws, hipStream_t stream);
+
 /* Row-softmax cross-entropy family over the strided logit view z[r][c] = logits[r*s_row + c*s_col], r < N, c < C
  * (replaces: nn.CrossEntropyLoss, ClassificationTrainer trainer.py:249,300; FocalLoss losses.py:90-116;
  * LabelSmoothingCrossEntropy losses.py:119-150; both F.cross_entropy of InfoNCELoss losses.py:76-85).
