@@ -89,6 +89,9 @@ _SIGS = {
     'cmhar_sim_topk_ws': (i64, [i32, i32, i32]),
     'cmhar_sim_topk_splits': (i32, [i32, i32, i32]),
     'cmhar_sim_topk': (i32, [i32, i32, i32, i32, i32, vp, i64, vp, i64, i64, vp, vp, vp, vp]),
+    'cmhar_class_moments_ws': (i64, [i32, i32, i32]),
+    'cmhar_class_moments': (i32, [i32, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp]),
+    'cmhar_class_min_dist': (i32, [i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp]),
     'cmhar_cross_entropy_ws': (i64, [i32]),
     'cmhar_resize_ksize': (i32, [i32, i32]),
     'cmhar_video_ingest_ws': (i64, [i32, i32, i32, i32, i32]),

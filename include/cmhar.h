@@ -240,6 +240,31 @@ int cmhar_sim_topk_splits(int nq, int nb, int k);
 int cmhar_sim_topk(int dtype, int nq, int nb, int d, int k, const void* q, long ldq, const void* bank, long ldb,
                    long self_offset, float* vals, int* idx, void* ws, hipStream_t stream);
 
+/* Class-conditional Gaussian (Mahalanobis) OOD detector, Lee et al. 2018 (no reference counterpart: the reference
+ * has no OOD code).  Both entries compute in exact fp32 on the f32-input MFMA; bf16 / fp16 x is widened on load
+ * (exact); there is no 16-bit math mode and no fp32 atomic, so the outputs are a pure function of the inputs, equal
+ * to the bit from run to run.  Inputs are assumed finite.  Supported: x [N, d] `dtype` rows of stride ldx elements,
+ * unit inner stride, 16-byte aligned rows (pointer; ldx % 8 == 0 for 16-bit, % 4 for fp32), 32 <= d <= 1024 with
+ * d % 32 == 0, 1 <= C <= 128, N >= 1; anything else returns hipErrorInvalidValue, launches nothing and leaves every
+ * output untouched.
+ *
+ * cmhar_class_moments: labels device int64 [N]; rows whose label is outside [0, C) contribute to nothing.
+ * counts[c] = #rows labelled c; means [C, d] row-major = the class means (an empty class: zeros, never NaN); scatter
+ * [d, d] row-major, exactly symmetric = Σ_i (x_i − μ_{y_i})(x_i − μ_{y_i})ᵀ, computed in a second pass from rows
+ * centred while they are staged (not as XᵀX − Σ n_c μ_c μ_cᵀ, which cancels).  means and ws 16-byte aligned;
+ * ws: cmhar_class_moments_ws(N, d, C) BYTES, always needed.
+ *
+ * cmhar_class_min_dist: z = W·x per row (W [d, d] fp32, row j gives z_j, row stride ldw), D[c] = Σ_j (z_j − m[c][j])²
+ * summed in this difference form (m [C, d] fp32, row stride ldm; W and m rows 16-byte aligned), dist2[i] = min_c D[c],
+ * cls[i] = the first index attaining it, dist_all[i][c] = D[c] (row stride ld_all >= C).  dist2, cls and dist_all
+ * are nullable.  z and the N x C x d differences never reach memory. */
+long cmhar_class_moments_ws(int N, int d, int C);
+int cmhar_class_moments(int dtype, int N, int d, int C, const void* x, long ldx, const long* labels, int* counts,
+                        float* means, float* scatter, void* ws, hipStream_t stream);
+int cmhar_class_min_dist(int dtype, int N, int d, int C, const void* x, long ldx, const float* W, long ldw,
+                         const float* m, long ldm, float* dist2, int* cls, float* dist_all, long ld_all,
+                         hipStream_t stream);
+
 /* Row-softmax cross-entropy family over the strided logit view z[r][c] = logits[r*s_row + c*s_col], r < N, c < C
  * (replaces: nn.CrossEntropyLoss, ClassificationTrainer trainer.py:249,300; FocalLoss losses.py:90-116;
  * LabelSmoothingCrossEntropy losses.py:119-150; both F.cross_entropy of InfoNCELoss losses.py:76-85).
