@@ -500,9 +500,11 @@ def layernorm_bwd(dy, h, gamma, mean, rstd, dgamma, dbeta, *, dres=None, dh=None
     return dh
 
 
-def batchnorm_fwd(x, w, b, rmean, rvar, training, momentum, eps, relu, num_batches_tracked=None):
+def batchnorm_fwd(x, w, b, rmean, rvar, training, momentum, eps, relu, num_batches_tracked=None, out=None):
     B, Cc = x.shape
-    y = torch.empty_like(x)
+    y = torch.empty_like(x) if out is None else out
+    if y.shape != x.shape or y.dtype != torch.float32 or not y.is_contiguous():
+        raise ValueError('batchnorm_fwd: out must be a contiguous fp32 tensor of x\'s shape')
     sm = torch.empty(Cc, dtype=torch.float32, device=x.device)
     sr = torch.empty(Cc, dtype=torch.float32, device=x.device)
     call('cmhar_batchnorm_fwd', B, Cc, ptr(x), ptr(y), ptr(w), ptr(b), ptr(rmean), ptr(rvar), ptr(sm), ptr(sr),
@@ -510,13 +512,19 @@ def batchnorm_fwd(x, w, b, rmean, rvar, training, momentum, eps, relu, num_batch
     return y, sm, sr
 
 
-def batchnorm_bwd(x, y, dy, w, sm, sr, training, relu):
+def batchnorm_bwd(x, y, dy, w, sm, sr, training, relu, beta_acc=0.0, dw=None, db=None):
+    """dw / db (optional, contiguous fp32 [C]): written as Σ + beta_acc·old (beta_acc = 1 accumulates into them)."""
     B, Cc = x.shape
     dx = torch.empty_like(x)
-    dw = torch.empty(Cc, dtype=torch.float32, device=x.device)
-    db = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    if dw is None:
+        dw = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    if db is None:
+        db = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    for t, n in ((dw, 'dw'), (db, 'db')):
+        if t.dtype != torch.float32 or tuple(t.shape) != (Cc,) or not t.is_contiguous():
+            raise ValueError(f'batchnorm_bwd: {n} must be a contiguous fp32 [{Cc}] tensor')
     call('cmhar_batchnorm_bwd', B, Cc, ptr(x), ptr(y), ptr(dy.contiguous()), ptr(w), ptr(sm), ptr(sr), ptr(dx),
-         ptr(dw), ptr(db), int(training), int(relu), 0.0, L.stream(x.device))
+         ptr(dw), ptr(db), int(training), int(relu), beta_acc, L.stream(x.device))
     return dx, dw, db
 
 

@@ -153,7 +153,8 @@ __global__ __launch_bounds__(256) void xent_rows(int N, int C, const float* __re
     } else {
       const float lse = m + __logf(s);
       const float zy = z[y * s_col];
-      const float ce = (1.f - eps) * (lse - zy) + eps * (lse - sz / (float)C);
+      // eps == 0: no smoothing term (a masked, -inf logit makes sz = -inf and 0·inf = NaN; torch's loss is finite)
+      const float ce = eps != 0.f ? (1.f - eps) * (lse - zy) + eps * (lse - sz / (float)C) : lse - zy;
       if (gamma != 0.f) {
         const float pt = __expf(-ce);
         l = alpha * __powf(fmaxf(1.f - pt, 0.f), gamma) * ce;
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(256) void xent_grad(int N, int C, const float* __re
   float w_q = alpha, w_h = 0.f;                 // dz = w_q·(p - q) + w_h·(p - onehot)
   if (!skip && gamma != 0.f) {
     const float zy = z[y * s_col];
-    const float ce = (1.f - eps) * (lse - zy) + eps * (lse - sz / (float)C);
+    const float ce = eps != 0.f ? (1.f - eps) * (lse - zy) + eps * (lse - sz / (float)C) : lse - zy;
     const float pt = __expf(-ce), om = fmaxf(1.f - pt, 0.f);
     w_q = alpha * __powf(om, gamma);
     w_h = om > 0.f ? alpha * gamma * __powf(om, gamma - 1.f) * pt * ce : 0.f;

@@ -549,6 +549,8 @@ extern "C" int cmhar_layernorm_bwd(int dtype, int M, int N, const void* dy, long
                                    long ldres, void* dh, long lddh, void* db_out, long lddb, float pdrop,
                                    unsigned long long seed, float* dgamma, float* dbeta, float beta_acc, float* ws,
                                    hipStream_t st) {
+  // fp16 is the inference-only path (no backward kernels): refused before any launch, like cmhar_attention_bwd
+  if (dtype != CMHAR_F32 && dtype != CMHAR_BF16) return -1;
   if (M <= 0) return 0;
   if (N > 64 * MAXPER) return -1;
   const bool vec = !db_out && ln_vec_ok(N, lddy, ldh, lddh) && (!dres || ldres % 4 == 0);
@@ -597,6 +599,8 @@ extern "C" long cmhar_colsum_ws(int M, int N) {
 
 extern "C" int cmhar_colsum(int dtype, int M, int N, const void* X, long ldx, float* out, float alpha, float beta,
                             float* ws, long ws_floats, hipStream_t st) {
+  // bias gradients are fp32 or bf16; fp16 (inference only) has no instantiation and is refused before any launch
+  if (dtype != CMHAR_F32 && dtype != CMHAR_BF16) return -1;
   if (N <= 0) return 0;
   const int rpc = cs_rows(M), chunks = cdiv(M, rpc);
   if ((long)chunks * N + reduce_rows_ws(chunks, N) > ws_floats) return -2;

@@ -127,7 +127,8 @@ int cmhar_attention_bwd_prescaled(int B, int H, int Lq, int Lk, const void* Q, l
 
 /* y = LayerNorm(a + dropout(b)) (b nullable); h_out (nullable) receives a + dropout(b)
  * (replaces: VideoMAE layernorm_before/after modeling_videomae.py:337-350, IMU post-LN norm1/norm2 and
- * final norm models.py:85-95,127). */
+ * final norm models.py:85-95,127).  The forward takes all three dtypes; the backward is fp32 / bf16 only: fp16 is
+ * the inference path, and cmhar_layernorm_bwd returns -1 for it before any launch (dh, dgamma, dbeta untouched). */
 int cmhar_layernorm_fwd(int dtype, int M, int N, const void* a, long lda, const void* b, long ldb, float pdrop,
                         unsigned long long seed, void* h_out, long ldh, void* y, long ldy, const float* gamma,
                         const float* beta, float* mean, float* rstd, float eps, hipStream_t stream);
@@ -137,7 +138,8 @@ int cmhar_layernorm_bwd(int dtype, int M, int N, const void* dy, long lddy, cons
                         void* dh, long lddh, void* db_out, long lddb, float pdrop, unsigned long long seed,
                         float* dgamma, float* dbeta, float beta_acc, float* ws, hipStream_t stream);
 
-/* out[n] = alpha Σ_m X[m,n] + beta out[n]  (bias gradients).  ws: cmhar_colsum_ws(M,N) floats. */
+/* out[n] = alpha Σ_m X[m,n] + beta out[n]  (bias gradients).  ws: cmhar_colsum_ws(M,N) floats.  X is fp32 or bf16;
+ * fp16 (inference only, no gradients) returns -1 before any launch and leaves out untouched. */
 long cmhar_colsum_ws(int M, int N);
 int cmhar_colsum(int dtype, int M, int N, const void* X, long ldx, float* out, float alpha, float beta, float* ws,
                  long ws_floats, hipStream_t stream);
@@ -273,7 +275,9 @@ int cmhar_class_min_dist(int dtype, int N, int d, int C, const void* x, long ldx
  * 2 sum.  Outputs (all nullable): loss scalar, row_loss [N], pred (first argmax) [N], correct = #(pred == label),
  * status = 1 when a label is out of range (the host raises).  dlogits (nullable, strides d_row/d_col):
  * dlogits = grad_beta*dlogits + grad_scale*g*dloss/dz, g = g_up[r] ('none', required) or (*g_up or 1) x (1/count
- * for 'mean').  ws: cmhar_cross_entropy_ws(N) floats. */
+ * for 'mean').  ws: cmhar_cross_entropy_ws(N) floats.
+ * -inf logits (masked classes) outside the target: with label_smoothing = 0 the loss and gradients are finite, as
+ * F.cross_entropy's (the smoothing term is not formed); with label_smoothing > 0 the loss is +inf, as torch's. */
 long cmhar_cross_entropy_ws(int N);
 int cmhar_cross_entropy(int N, int C, const float* logits, long s_row, long s_col, const long* labels,
                         long ignore_index, float label_smoothing, float gamma, float alpha, int reduction, float* loss,

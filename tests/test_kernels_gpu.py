@@ -2,7 +2,11 @@
 
 Tolerances are written per test: exact-fp32 kernels ≤ 1e-5 relative; bf16-operand kernels are compared with the
 fp32 reference evaluated ON THE SAME bf16-ROUNDED INPUTS, so the only differences are accumulation order
-(fp32) and the final bf16 rounding of outputs (≤ 2^-8 relative)."""
+(fp32) and the final bf16 rounding of outputs (≤ 2^-8 relative).
+
+The norm / reduction / copy / loss kernels have their dispatch paths and edge shapes walked against fp64 references in
+tests/test_rowops_gpu.py and tests/test_loss_kernels_gpu.py; the "norms / small ops" block here keeps the production
+shapes."""
 import math
 
 import numpy as np
