@@ -86,6 +86,9 @@ _SIGS = {
                                     vp, vp, vp, vp, vp, vp, vp, f32, f32, u64, vp]),
     'cmhar_copy2d': (i32, [i32, i32, i32, i32, vp, i64, vp, i64, f32, f32, f32, u64, vp]),
     'cmhar_logits_energy': (i32, [i32, i32, i32, vp, i64, f32, vp, vp, vp, vp]),
+    'cmhar_pair_sigmoid_ws': (i64, [i32, i32, i32]),
+    'cmhar_pair_sigmoid_loss': (i32, [i32, i32, i32, vp, i64, vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, i32, vp, i32,
+                                      i32, vp, vp, vp, vp]),
     'cmhar_sim_topk_ws': (i64, [i32, i32, i32]),
     'cmhar_sim_topk_splits': (i32, [i32, i32, i32]),
     'cmhar_sim_topk': (i32, [i32, i32, i32, i32, i32, vp, i64, vp, i64, i64, vp, vp, vp, vp]),

@@ -40,6 +40,8 @@ def resume(trainer, path, strict: bool = True, restore_optimizer: bool = True) -
     trainer.model.load_state_dict(strip_module_prefix(ckpt['model_state_dict']), strict=strict)
     trainer.current_epoch = int(ckpt.get('epoch', 0))
     trainer.history = ckpt.get('history', {'train': [], 'val': []})
+    if 'loss_state_dict' in ckpt and getattr(trainer, 'train_loss_params', False):
+        trainer.loss_fn.load_state_dict(ckpt['loss_state_dict'], strict=strict)   # CrossModalTrainer(train_loss_params=True)
     if restore_optimizer and 'optimizer_state_dict' in ckpt:
         trainer.optimizer.load_state_dict(ckpt['optimizer_state_dict'])
         # (the backbone's bf16 weight packs re-cast themselves: load_state_dict bumped the masters' versions)

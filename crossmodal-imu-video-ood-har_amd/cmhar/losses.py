@@ -1,4 +1,5 @@
-"""SigmoidContrastiveLoss (`src/models/losses.py:9-54`) on the fused cmhar loss kernel.
+"""SigmoidContrastiveLoss (`src/models/losses.py:9-54`) on the fused cmhar loss kernel, and (further down)
+`PairwiseSigmoidLoss`, the real SigLIP loss next to it.
 
 Same constructor (`init_temperature=10.0, init_bias=-10.0, learnable=True`), same parameters / buffers
 (`temperature` = log(init_temperature), `bias`), same value: the reference's BCE-with-logits over
@@ -106,6 +107,146 @@ class SigmoidContrastiveLoss(nn.Module):
             from . import dist as _d
             group = _d.loss_group()
         return _SigLIPFn.apply(imu_embeds, video_embeds, self.temperature, self.bias, group)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# PairwiseSigmoidLoss: the pairwise-sigmoid loss of SigLIP (Zhai et al. 2023) on the tiled fused kernel
+# `cmhar_pair_sigmoid_loss`.  No reference counterpart: the reference's `losses.py:44-52` is meant to be this loss,
+# but its labels cancel and `SigmoidContrastiveLoss` above keeps that for parity.  Here the
+# diagonal pairs are positives and every other pair a negative, normalised by the batch size as in the paper; with
+# `labels`, off-diagonal pairs of one group (same activity class, same recording: the overlapping windows of HAR
+# batches) can be left out of the loss or counted as positives instead of being pushed apart.
+# ------------------------------------------------------------------------------------------------------------------
+_SAME_GROUP = {'negative': 0, 'ignore': 1, 'positive': 2}
+_PAIR_MAX_B, _PAIR_MAX_D = 32768, 1024
+
+
+def _gather_labels(labels, group):
+    if group is None:
+        return labels
+    import torch.distributed as dist
+    out = torch.empty(dist.get_world_size(group) * labels.shape[0], dtype=labels.dtype, device=labels.device)
+    dist.all_gather_into_tensor(out, labels, group=group)
+    return out
+
+
+def pair_sigmoid_raw(a, b, t, bias, ga=None, gb=None, same_group=0, a_rows=None, b_rows=None, want_t=True):
+    """`cmhar_pair_sigmoid_loss` on device tensors: a [Ba, D], b [Bb, D] fp32 with unit inner stride (row strides are
+    passed on), t / bias one-element device tensors, ga / gb int64 group ids or None.  `a_rows` / `b_rows`: (off, cnt)
+    of the gradient rows wanted, None: no gradient for that side.  Returns (loss, da, db, gt, gbias); the gradients
+    not asked for are None."""
+    dev = a.device
+    Ba, D = a.shape
+    Bb = b.shape[0]
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    da = torch.empty(a_rows[1], D, dtype=torch.float32, device=dev) if a_rows is not None else None
+    db = torch.empty(b_rows[1], D, dtype=torch.float32, device=dev) if b_rows is not None else None
+    gt = torch.empty(1, dtype=torch.float32, device=dev) if want_t else None
+    gbias = torch.empty(1, dtype=torch.float32, device=dev) if want_t else None
+    ws = K.workspace((L.lib().cmhar_pair_sigmoid_ws(Ba, Bb, D) + 3) // 4, dev)
+    a_off, a_cnt = a_rows if a_rows is not None else (0, 0)
+    b_off, b_cnt = b_rows if b_rows is not None else (0, 0)
+    L.call('cmhar_pair_sigmoid_loss', Ba, Bb, D, a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), L.ptr(ga),
+           L.ptr(gb), int(same_group), t.data_ptr(), bias.data_ptr(), loss.data_ptr(), L.ptr(da), a_off, a_cnt,
+           L.ptr(db), b_off, b_cnt, L.ptr(gt), L.ptr(gbias), ws.data_ptr(), L.stream(dev))
+    return loss, da, db, gt, gbias
+
+
+class _PairSigmoidFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a_local, b_local, t, bias, labels, mode, group, want_grad):
+        dev = a_local.device
+        a_local = a_local.contiguous().float()
+        b_local = b_local.contiguous().float()
+        Bl, D = a_local.shape
+        a_all, b_all, off = gather_global(a_local, b_local, group)
+        if a_all.shape[0] > _PAIR_MAX_B:
+            raise ValueError(f'global batch {a_all.shape[0]} exceeds {_PAIR_MAX_B}')
+        ids = _gather_labels(labels, group) if labels is not None else None
+        t_dev = t.detach().reshape(1).to(device=dev, dtype=torch.float32)
+        b_dev = bias.detach().reshape(1).to(device=dev, dtype=torch.float32)
+        rows = (off, Bl) if want_grad else None
+        loss, da, db, gt, gb = pair_sigmoid_raw(a_all, b_all, t_dev, b_dev, ids, ids, mode, rows, rows, want_grad)
+        if want_grad:
+            ctx.save_for_backward(da, db, gt, gb)
+            ctx.t_meta = (t.shape, t.device, t.dtype)
+            ctx.b_meta = (bias.shape, bias.device, bias.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        da, db, gt, gb = ctx.saved_tensors
+        ga = gbv = gtt = gbb = None
+        # scaling by the incoming (device) scalar gradient: a B×D elementwise product, no host sync
+        if ctx.needs_input_grad[0]:
+            ga = da * g
+        if ctx.needs_input_grad[1]:
+            gbv = db * g
+        if ctx.needs_input_grad[2]:
+            shape, dev, dt = ctx.t_meta
+            gtt = (gt * g).reshape(shape).to(device=dev, dtype=dt)
+        if ctx.needs_input_grad[3]:
+            shape, dev, dt = ctx.b_meta
+            gbb = (gb * g).reshape(shape).to(device=dev, dtype=dt)
+        return ga, gbv, gtt, gbb, None, None, None, None
+
+
+class PairwiseSigmoidLoss(nn.Module):
+    """Pairwise-sigmoid (SigLIP) loss: `Σ_ij w_ij·softplus(−z_ij·S_ij) / B`, S = a·bᵀ·exp(temperature) + bias, z = +1 on
+    the diagonal and −1 elsewhere.  `same_group` says what an off-diagonal pair with equal `labels` is: 'negative'
+    (plain SigLIP; labels are not needed), 'ignore' (left out of the sum) or 'positive'.  `temperature` (the log of
+    `init_temperature`) and `bias` are parameters when `learnable`, as in `SigmoidContrastiveLoss`; `group` as there:
+    the loss is over the global batch, gradient rows are this rank's, and the gradients of `temperature` / `bias`
+    are already the full-batch ones on every rank (do not sum them over ranks)."""
+
+    wants_labels = True
+
+    def __init__(self, init_temperature=10.0, init_bias=-10.0, learnable=True, same_group='negative', group=None):
+        super().__init__()
+        if same_group not in _SAME_GROUP:
+            raise ValueError(f"same_group must be one of {sorted(_SAME_GROUP)}, got {same_group!r}")
+        if learnable:
+            self.temperature = nn.Parameter(torch.tensor(init_temperature).log())
+            self.bias = nn.Parameter(torch.tensor(init_bias))
+        else:
+            self.register_buffer('temperature', torch.tensor(init_temperature).log())
+            self.register_buffer('bias', torch.tensor(init_bias))
+        self.same_group = same_group
+        self.group = group
+
+    def forward(self, imu_embeds, video_embeds, labels=None):
+        if imu_embeds.shape != video_embeds.shape or imu_embeds.dim() != 2:
+            raise ValueError('expected two (batch, dim) embedding matrices of equal shape')
+        B, D = imu_embeds.shape
+        if D < 1 or D > _PAIR_MAX_D:
+            raise ValueError(f'embedding dim {D} outside [1, {_PAIR_MAX_D}]')
+        if B < 1 or B > _PAIR_MAX_B:
+            raise ValueError(f'batch {B} outside [1, {_PAIR_MAX_B}]')
+        if self.same_group not in _SAME_GROUP:
+            raise ValueError(f"same_group must be one of {sorted(_SAME_GROUP)}, got {self.same_group!r}")
+        mode = _SAME_GROUP[self.same_group]
+        if labels is None:
+            if mode != 0:
+                raise ValueError(f"same_group={self.same_group!r} needs labels")
+        else:
+            labels = torch.as_tensor(labels)
+            if labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool:
+                raise ValueError(f'expected integer group ids, got {labels.dtype}')
+            if labels.dim() != 1 or labels.shape[0] != B:
+                raise ValueError(f'expected {B} group ids, got shape {tuple(labels.shape)}')
+            # 'negative' treats same-group pairs like any other: the ids are not read
+            labels = (labels.to(device=imu_embeds.device, dtype=torch.int64, non_blocking=True).contiguous()
+                      if mode != 0 else None)
+        group = self.group
+        if group is False:                 # explicitly local: this process's batch only
+            group = None
+        elif group is None:
+            from . import dist as _d
+            group = _d.loss_group()
+        want_grad = torch.is_grad_enabled() and any(
+            x.requires_grad for x in (imu_embeds, video_embeds, self.temperature, self.bias))
+        return _PairSigmoidFn.apply(imu_embeds, video_embeds, self.temperature, self.bias, labels, mode, group,
+                                    want_grad)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -254,6 +395,8 @@ def get_loss_function(loss_name, **kwargs):
     """Reference losses.py:153-167."""
     if loss_name == 'sigmoid_contrastive':
         return SigmoidContrastiveLoss(**kwargs)
+    if loss_name in ('siglip', 'pairwise_sigmoid'):   # no reference counterpart: the loss the reference meant
+        return PairwiseSigmoidLoss(**kwargs)
     if loss_name == 'infonce':
         return InfoNCELoss(**kwargs)
     if loss_name == 'cross_entropy':

@@ -100,21 +100,38 @@ class BaseTrainer:
 #   Cross-modal Pretraining Trainer  (trainer.py:62-230)
 # -----------------------------
 class CrossModalTrainer(BaseTrainer):
-    """Pretraining cross-modal IMU-Video; best = min val_loss."""
+    """Pretraining cross-modal IMU-Video; best = min val_loss.  `train_loss_params=True` (no reference counterpart:
+    the reference never optimises its loss's temperature and bias) also trains `loss_fn`'s
+    parameters; a `loss_fn` with `wants_labels` gets the batches' `'label'`."""
 
     def __init__(self, model, loss_fn, config, device: str = 'cuda', *, grad_reducer=None,
-                 show_progress: bool = False):
+                 show_progress: bool = False, train_loss_params: bool = False):
         super().__init__(model, config, device)
         self.loss_fn = loss_fn
+        self.train_loss_params = bool(train_loss_params)
+        # a loss that takes group ids (PairwiseSigmoidLoss) gets the batch's 'label' when there is one
+        self.loss_wants_labels = bool(getattr(loss_fn, 'wants_labels', False))
         self.best_val_loss = float('inf')
         self.grad_reducer = grad_reducer
         self.show_progress = show_progress
         # max_grad_norm: trainer.py:140's clip_grad_norm_(model.parameters(), 1.0) folded into the AdamW pass
         # (bit-identical update and post-clip .grad; one scale pass over the gradients less)
-        self.optimizer = FusedAdamW(self.model.parameters(), lr=config.training.pretrain_lr,
-                                    weight_decay=config.training.pretrain_weight_decay,
-                                    shadow_sources=_shadow_sources(self.model), max_grad_norm=1.0,
-                                    clip_params=self.model.parameters())
+        if self.train_loss_params:
+            # the loss's temperature and bias as a second group: same lr and schedule, no weight decay.  They are not
+            # handed to grad_reducer: every rank computes their full-batch gradient, a SUM would scale it by the
+            # world size.
+            self.loss_fn.to(device)
+            loss_params = [p for p in self.loss_fn.parameters() if p.requires_grad]
+            self.optimizer = FusedAdamW(
+                [{'params': list(self.model.parameters())}, {'params': loss_params, 'weight_decay': 0.0}],
+                lr=config.training.pretrain_lr, weight_decay=config.training.pretrain_weight_decay,
+                shadow_sources=_shadow_sources(self.model), max_grad_norm=1.0,
+                clip_params=list(self.model.parameters()) + loss_params)
+        else:
+            self.optimizer = FusedAdamW(self.model.parameters(), lr=config.training.pretrain_lr,
+                                        weight_decay=config.training.pretrain_weight_decay,
+                                        shadow_sources=_shadow_sources(self.model), max_grad_norm=1.0,
+                                        clip_params=self.model.parameters())
         num_epochs = int(config.training.pretrain_epochs)
         warmup_epochs = int(getattr(config.training, 'pretrain_warmup_epochs', 0))
         if warmup_epochs <= 0:
@@ -140,10 +157,22 @@ class CrossModalTrainer(BaseTrainer):
         video = batch['video'].to(self.device, non_blocking=True)
         return imu, self._maybe_permute_video(video).contiguous()
 
-    def train_step(self, imu, video):
-        """One step of trainer.py:135-141; returns the loss as a device scalar."""
+    def _labels(self, batch):
+        """The batch's group ids for a loss that wants them (None otherwise)."""
+        if self.loss_wants_labels and 'label' in batch:
+            return batch['label']
+        return None
+
+    def _loss(self, imu_proj, video_proj, labels):
+        if labels is None:
+            return self.loss_fn(imu_proj, video_proj)
+        return self.loss_fn(imu_proj, video_proj, labels=labels)
+
+    def train_step(self, imu, video, labels=None):
+        """One step of trainer.py:135-141; returns the loss as a device scalar.  `labels`: group ids for a loss with
+        `wants_labels`."""
         imu_proj, video_proj = self.model(imu, video)
-        loss = self.loss_fn(imu_proj, video_proj)
+        loss = self._loss(imu_proj, video_proj, labels)
         self.optimizer.zero_grad(set_to_none=True)
         if self.grad_reducer is not None:
             self.grad_reducer.start_step()
@@ -157,7 +186,7 @@ class CrossModalTrainer(BaseTrainer):
         self.model.train()
         total = _DeviceSum(self.device)
         for batch in _progress(dataloader, self.show_progress, f'[Pretrain] Epoch {self.current_epoch}'):
-            total.add(self.train_step(*self._batch(batch)))
+            total.add(self.train_step(*self._batch(batch), labels=self._labels(batch)))
         D.broadcast_buffers(self.model)     # rank 0's BN running statistics (DataParallel's device-0 replica)
         return total.value() / max(len(dataloader), 1)     # global-batch loss: identical on every rank
 
@@ -167,12 +196,15 @@ class CrossModalTrainer(BaseTrainer):
         total = _DeviceSum(self.device)
         for batch in _progress(dataloader, self.show_progress, '[Pretrain] Val'):
             imu_proj, video_proj = self.model(*self._batch(batch))
-            total.add(self.loss_fn(imu_proj, video_proj))
+            total.add(self._loss(imu_proj, video_proj, self._labels(batch)))
         return total.value() / max(len(dataloader), 1)
 
     def _extra(self):
-        return {'best_val_loss': self.best_val_loss, 'optimizer_state_dict': self.optimizer.state_dict(),
-                'scheduler_state_dict': self.scheduler.state_dict()}
+        extra = {'best_val_loss': self.best_val_loss, 'optimizer_state_dict': self.optimizer.state_dict(),
+                 'scheduler_state_dict': self.scheduler.state_dict()}
+        if self.train_loss_params:     # the trained temperature / bias belong to the run (cmhar.checkpoint.resume)
+            extra['loss_state_dict'] = self.loss_fn.state_dict()
+        return extra
 
     def fit(self, train_loader, val_loader):
         num_epochs = int(self.config.training.pretrain_epochs)

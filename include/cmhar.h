@@ -165,6 +165,26 @@ int cmhar_siglip_loss(int Ba, int Bb, int D, const float* a, const float* b, con
                       float* loss, float* da, int a_off, int a_cnt, float* db, int b_off, int b_cnt, float* gt,
                       float* gbias, float* ws, hipStream_t stream);
 
+/* PairwiseSigmoidLoss forward + gradients: the pairwise-sigmoid loss of SigLIP (Zhai et al. 2023, "Sigmoid Loss for
+ * Language Image Pre-Training"); a fix for src/models/losses.py:44-52, whose labels cancel: parity unpinned.
+ * a [Ba, D], b [Bb, D] fp32 rows of stride lda / ldb elements (unit inner stride; any alignment, any D <= 1024);
+ * S_ij = (a_i·b_j)·exp(t) + bias with t, bias device scalars.  Pair (i, j) is positive (z = +1) iff i == j; an
+ * off-diagonal pair with ga[i] == gb[j] (device int64 ids, or both NULL: no groups) is negative for same_group 0,
+ * ignored (w = 0) for 1, positive for 2; every other pair is negative (z = -1, w = 1).
+ *   loss = (1/Ba)·Σ_ij w_ij·softplus(-z_ij·S_ij),  dS_ij = -w_ij·z_ij·σ(-z_ij·S_ij)/Ba,
+ *   da [a_cnt, D] = e^t·Σ_j dS_ij·b_j for rows [a_off, a_off + a_cnt),  db [b_cnt, D] likewise for b,
+ *   gt = Σ dS_ij·(a_i·b_j)·e^t,  gbias = Σ dS_ij  (loss, gt, gbias always over ALL pairs).
+ * da, db, gt, gbias are nullable (skipped; with da and db NULL no gradient product runs).  The Ba x Bb matrix never
+ * reaches memory; dot products and gradient products run in exact fp32 on the f32-input MFMA in a fixed order and
+ * there is no fp32 atomic, so every output is a pure function of the inputs, independent of the offsets / counts.
+ * Supported: 1 <= Ba, Bb <= 32768, 1 <= D <= 1024, same_group in {0, 1, 2}; anything else returns -1 and writes
+ * nothing.  ws: cmhar_pair_sigmoid_ws(Ba, Bb, D) BYTES (O(Ba), never O(Ba·Bb)). */
+long cmhar_pair_sigmoid_ws(int Ba, int Bb, int D);
+int cmhar_pair_sigmoid_loss(int Ba, int Bb, int D, const float* a, long lda, const float* b, long ldb,
+                            const long* ga, const long* gb, int same_group, const float* t, const float* bias,
+                            float* loss, float* da, int a_off, int a_cnt, float* db, int b_off, int b_cnt, float* gt,
+                            float* gbias, void* ws, hipStream_t stream);
+
 /* VideoMAE tubelet patches (replaces: the Conv3d input side, modeling_videomae.py:159-168). */
 int cmhar_tubelet_im2col(int out_dtype, int B, int T, int C, int H, int W, int tub, int P, const float* video,
                          void* out, hipStream_t stream);
