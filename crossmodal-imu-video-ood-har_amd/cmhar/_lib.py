@@ -89,6 +89,9 @@ _SIGS = {
     'cmhar_pair_sigmoid_ws': (i64, [i32, i32, i32]),
     'cmhar_pair_sigmoid_loss': (i32, [i32, i32, i32, vp, i64, vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, i32, vp, i32,
                                       i32, vp, vp, vp, vp]),
+    'cmhar_softmax_contrast_ws': (i64, [i32, i32]),
+    'cmhar_softmax_contrast_loss': (i32, [i32, i32, vp, i64, vp, i64, vp, i32, vp, vp, vp, i32, i32, vp, i32, i32, vp,
+                                          vp, vp]),
     'cmhar_sim_topk_ws': (i64, [i32, i32, i32]),
     'cmhar_sim_topk_splits': (i32, [i32, i32, i32]),
     'cmhar_sim_topk': (i32, [i32, i32, i32, i32, i32, vp, i64, vp, i64, i64, vp, vp, vp, vp]),

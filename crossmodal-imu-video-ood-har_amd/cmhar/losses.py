@@ -1,5 +1,6 @@
 """SigmoidContrastiveLoss (`src/models/losses.py:9-54`) on the fused cmhar loss kernel, and (further down)
-`PairwiseSigmoidLoss`, the real SigLIP loss next to it.
+`PairwiseSigmoidLoss`, the real SigLIP loss next to it, the cross-entropy family with `InfoNCELoss`, and
+`SoftmaxContrastiveLoss`, the softmax contrastive loss on its own tiled kernel.
 
 Same constructor (`init_temperature=10.0, init_bias=-10.0, learnable=True`), same parameters / buffers
 (`temperature` = log(init_temperature), `bias`), same value: the reference's BCE-with-logits over
@@ -391,6 +392,125 @@ class InfoNCELoss(nn.Module):
         return _InfoNCEFn.apply(imu_embeds, video_embeds, 1.0 / self.temperature)
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# SoftmaxContrastiveLoss: the softmax contrastive loss (CLIP / InfoNCE, the reference's losses.py:57-87) on the tiled
+# two-pass kernel `cmhar_softmax_contrast_loss`.  Next to `InfoNCELoss` above (kept as it is, the composite of GEMM and
+# cross-entropy launches that stores S and dS) it never stores the B×B matrix, works over the data-parallel global
+# batch, has a learnable logit scale, and with `labels` can leave same-group pairs out of the softmax denominators or
+# count them as positives (the cross-modal supervised-contrastive form).
+# ------------------------------------------------------------------------------------------------------------------
+def softmax_contrast_raw(a, b, t, ids=None, same_group=0, a_rows=None, b_rows=None, want_t=True):
+    """`cmhar_softmax_contrast_loss` on device tensors: a, b [B, D] fp32 with unit inner stride (row strides are passed
+    on), t a one-element device tensor, ids int64 group ids or None.  `a_rows` / `b_rows`: (off, cnt) of the gradient
+    rows wanted, None: no gradient for that side.  Returns (loss, da, db, gt); the gradients not asked for are None."""
+    dev = a.device
+    B, D = a.shape
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    da = torch.empty(a_rows[1], D, dtype=torch.float32, device=dev) if a_rows is not None else None
+    db = torch.empty(b_rows[1], D, dtype=torch.float32, device=dev) if b_rows is not None else None
+    gt = torch.empty(1, dtype=torch.float32, device=dev) if want_t else None
+    ws = K.workspace((L.lib().cmhar_softmax_contrast_ws(B, D) + 3) // 4, dev)
+    a_off, a_cnt = a_rows if a_rows is not None else (0, 0)
+    b_off, b_cnt = b_rows if b_rows is not None else (0, 0)
+    L.call('cmhar_softmax_contrast_loss', B, D, a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), L.ptr(ids),
+           int(same_group), t.data_ptr(), loss.data_ptr(), L.ptr(da), a_off, a_cnt, L.ptr(db), b_off, b_cnt,
+           L.ptr(gt), ws.data_ptr(), L.stream(dev))
+    return loss, da, db, gt
+
+
+class _SoftmaxContrastFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a_local, b_local, t, labels, mode, group, want_grad):
+        dev = a_local.device
+        a_local = a_local.contiguous().float()
+        b_local = b_local.contiguous().float()
+        Bl, D = a_local.shape
+        a_all, b_all, off = gather_global(a_local, b_local, group)
+        if a_all.shape[0] > _PAIR_MAX_B:
+            raise ValueError(f'global batch {a_all.shape[0]} exceeds {_PAIR_MAX_B}')
+        ids = _gather_labels(labels, group) if labels is not None else None
+        t_dev = t.detach().reshape(1).to(device=dev, dtype=torch.float32)
+        rows = (off, Bl) if want_grad else None
+        loss, da, db, gt = softmax_contrast_raw(a_all, b_all, t_dev, ids, mode, rows, rows, want_grad)
+        if want_grad:
+            ctx.save_for_backward(da, db, gt)
+            ctx.t_meta = (t.shape, t.device, t.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        da, db, gt = ctx.saved_tensors
+        ga = gbv = gtt = None
+        # scaling by the incoming (device) scalar gradient: a B×D elementwise product, no host sync
+        if ctx.needs_input_grad[0]:
+            ga = da * g
+        if ctx.needs_input_grad[1]:
+            gbv = db * g
+        if ctx.needs_input_grad[2]:
+            shape, dev, dt = ctx.t_meta
+            gtt = (gt * g).reshape(shape).to(device=dev, dtype=dt)
+        return ga, gbv, gtt, None, None, None, None
+
+
+class SoftmaxContrastiveLoss(nn.Module):
+    """Symmetric softmax contrastive loss (CLIP / InfoNCE): the mean over rows and over columns of
+    `logsumexp(S) − S_positive`, halved, with S = a·bᵀ·exp(temperature).  `temperature` is the LOG of the logit scale
+    `init_temperature`, as in the two sigmoid losses: `InfoNCELoss(temperature=τ)` corresponds to
+    `init_temperature=1/τ` (the default 1/0.07 is `InfoNCELoss`'s default); it is a parameter when `learnable`, else
+    a buffer.  `same_group` says what an off-diagonal pair with equal `labels` is: 'negative' (plain CLIP; labels are
+    not needed), 'ignore' (left out of both softmax denominators) or 'positive' (the supervised-contrastive form: the
+    mean log-probability over a row's positives, in both directions).  `group` as in `PairwiseSigmoidLoss`: None is
+    `cmhar.dist.loss_group()`, False this process's batch only; the loss is over the global batch, gradient rows are
+    this rank's, and the gradient of `temperature` is already the full-batch one on every rank (do not sum it over
+    ranks)."""
+
+    wants_labels = True
+
+    def __init__(self, init_temperature=1 / 0.07, learnable=True, same_group='negative', group=None):
+        super().__init__()
+        if same_group not in _SAME_GROUP:
+            raise ValueError(f"same_group must be one of {sorted(_SAME_GROUP)}, got {same_group!r}")
+        if learnable:
+            self.temperature = nn.Parameter(torch.tensor(float(init_temperature)).log())
+        else:
+            self.register_buffer('temperature', torch.tensor(float(init_temperature)).log())
+        self.same_group = same_group
+        self.group = group
+
+    def forward(self, imu_embeds, video_embeds, labels=None):
+        if imu_embeds.shape != video_embeds.shape or imu_embeds.dim() != 2:
+            raise ValueError('expected two (batch, dim) embedding matrices of equal shape')
+        B, D = imu_embeds.shape
+        if D < 1 or D > _PAIR_MAX_D:
+            raise ValueError(f'embedding dim {D} outside [1, {_PAIR_MAX_D}]')
+        if B < 1 or B > _PAIR_MAX_B:
+            raise ValueError(f'batch {B} outside [1, {_PAIR_MAX_B}]')
+        if self.same_group not in _SAME_GROUP:
+            raise ValueError(f"same_group must be one of {sorted(_SAME_GROUP)}, got {self.same_group!r}")
+        mode = _SAME_GROUP[self.same_group]
+        if labels is None:
+            if mode != 0:
+                raise ValueError(f"same_group={self.same_group!r} needs labels")
+        else:
+            labels = torch.as_tensor(labels)
+            if labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool:
+                raise ValueError(f'expected integer group ids, got {labels.dtype}')
+            if labels.dim() != 1 or labels.shape[0] != B:
+                raise ValueError(f'expected {B} group ids, got shape {tuple(labels.shape)}')
+            # 'negative' treats same-group pairs like any other: the ids are not read
+            labels = (labels.to(device=imu_embeds.device, dtype=torch.int64, non_blocking=True).contiguous()
+                      if mode != 0 else None)
+        group = self.group
+        if group is False:                 # explicitly local: this process's batch only
+            group = None
+        elif group is None:
+            from . import dist as _d
+            group = _d.loss_group()
+        want_grad = torch.is_grad_enabled() and any(
+            x.requires_grad for x in (imu_embeds, video_embeds, self.temperature))
+        return _SoftmaxContrastFn.apply(imu_embeds, video_embeds, self.temperature, labels, mode, group, want_grad)
+
+
 def get_loss_function(loss_name, **kwargs):
     """Reference losses.py:153-167."""
     if loss_name == 'sigmoid_contrastive':
@@ -399,6 +519,10 @@ def get_loss_function(loss_name, **kwargs):
         return PairwiseSigmoidLoss(**kwargs)
     if loss_name == 'infonce':
         return InfoNCELoss(**kwargs)
+    if loss_name in ('softmax_contrastive', 'clip'):  # the same loss on the tiled kernel: global batch, labels
+        return SoftmaxContrastiveLoss(**kwargs)
+    if loss_name == 'supcon':                         # its supervised-contrastive form
+        return SoftmaxContrastiveLoss(**{'same_group': 'positive', **kwargs})
     if loss_name == 'cross_entropy':
         return CrossEntropyLoss(**kwargs)
     if loss_name == 'focal':

@@ -185,6 +185,31 @@ int cmhar_pair_sigmoid_loss(int Ba, int Bb, int D, const float* a, long lda, con
                             float* loss, float* da, int a_off, int a_cnt, float* db, int b_off, int b_cnt, float* gt,
                             float* gbias, void* ws, hipStream_t stream);
 
+/* SoftmaxContrastiveLoss forward + gradients: the symmetric softmax contrastive loss (CLIP / InfoNCE; replaces:
+ * src/models/losses.py:57-87 with e^t = 1/temperature) over the whole batch, and with group ids its cross-modal
+ * supervised-contrastive form.  a, b [B, D] fp32 rows of stride lda / ldb elements (unit inner stride; any alignment,
+ * any D <= 1024); S_ij = (a_i·b_j)·exp(t) with t a device scalar (no bias: a softmax does not see one).  ids: device
+ * int64 group of pair i, the same for a_i and b_i, or NULL (no groups).  An off-diagonal pair with ids[i] == ids[j]
+ * is an ordinary negative for same_group 0, left out of both softmax denominators for 1 (V_ij = 0; the diagonal
+ * never is), and one more positive of row i and of column j for 2 (P_i = {i} ∪ {j : ids[j] == ids[i]}, n_i = |P_i|;
+ * otherwise P_i = {i}).
+ *   lse_r[i] = log Σ_j V_ij e^{S_ij},  lse_c[j] = log Σ_i V_ij e^{S_ij},
+ *   loss = 1/(2B)·Σ_i [lse_r[i] − (1/n_i) Σ_{p∈P_i} S_ip + lse_c[i] − (1/n_i) Σ_{p∈P_i} S_pi],
+ *   dS_ij = 1/(2B)·[V_ij (e^{S_ij − lse_r[i]} + e^{S_ij − lse_c[j]}) − 2·[j ∈ P_i]/n_i],
+ *   da [a_cnt, D] = e^t·Σ_j dS_ij·b_j for rows [a_off, a_off + a_cnt),  db [b_cnt, D] likewise for b,
+ *   gt = Σ dS_ij·S_ij  (loss and gt always over ALL pairs).
+ * da, db, gt are nullable (skipped); loss and gt come out of the first of two passes over S, so with da and db NULL
+ * the second pass and its gradient products do not run.  The B x B matrix never reaches memory; the softmax is an
+ * online one with the running maximum subtracted (rows need not be unit-norm), dot products and gradient products
+ * run in exact fp32 on the f32-input MFMA in a fixed order and there is no fp32 atomic, so every output is a pure
+ * function of the inputs, independent of the offsets / counts.  Supported: 1 <= B <= 32768, 1 <= D <= 1024,
+ * same_group in {0, 1, 2}; anything else returns -1 and writes nothing.  ws: cmhar_softmax_contrast_ws(B, D) BYTES
+ * (O(B): row / column statistics and strip sums). */
+long cmhar_softmax_contrast_ws(int B, int D);
+int cmhar_softmax_contrast_loss(int B, int D, const float* a, long lda, const float* b, long ldb, const long* ids,
+                                int same_group, const float* t, float* loss, float* da, int a_off, int a_cnt,
+                                float* db, int b_off, int b_cnt, float* gt, void* ws, hipStream_t stream);
+
 /* VideoMAE tubelet patches (replaces: the Conv3d input side, modeling_videomae.py:159-168). */
 int cmhar_tubelet_im2col(int out_dtype, int B, int T, int C, int H, int W, int tub, int P, const float* video,
                          void* out, hipStream_t stream);
