@@ -61,23 +61,10 @@ def _conv(cin, cout, k, s, p):
 
 
 def _plans(cin, cout, k, s, p, shape):
-    from cmhar import _lib as L
-    from cmhar import r3d
-    lib = L.lib()
-    conv = _conv(cin, cout, k, s, p)
-    shp = tuple(shape) + (cin,)
-    Kp = r3d._r8(conv.weight[0].numel())
-    dims = r3d._dims(shp, conv, Kp)
-    fwd = 'split' if lib.cmhar_conv3d_fwd_split_ws(dims, cout) > 0 else lib.cmhar_conv3d_fwd_plan(dims, cout)
-    if r3d._dgrad_igemm_ok(conv):
-        N, To, Ho, Wo, _ = r3d._out_shape(shp, conv)
-        kt, kh, kw = conv.kernel_size
-        fd = r3d._dims((N, To, Ho, Wo, cout), _conv(cout, cin, k, 1, p), kt * kh * kw * cout)
-        dg = 'flip:' + str('split' if lib.cmhar_conv3d_fwd_split_ws(fd, cin) > 0 else lib.cmhar_conv3d_fwd_plan(fd, cin))
-    else:
-        dg = 'col2im'
-    wg = str(lib.cmhar_conv3d_wgrad_plan(dims, cout)) + ('+r' if lib.cmhar_conv3d_wgrad_ws(dims, cout) > 0 else '')
-    return fwd, dg, wg
+    """(forward, input gradient, weight gradient) plans of one conv: the library's host-side queries, shared with
+    tests/test_conv_plans_gpu.py (tests/conv_exact.py)."""
+    from conv_exact import plans
+    return plans(cin, cout, k, s, p, shape)
 
 
 def test_r3d_production_plans():
