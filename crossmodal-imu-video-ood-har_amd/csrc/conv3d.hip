@@ -5,57 +5,30 @@
 // kt·kh·kw contiguous C-vectors and a convolution is a GEMM over rows = output positions:
 //   col[m, k] (k = ((it·kh + ih)·kw + iw)·C + c, zero-padded to Kp)  →  y[m, co] = col[m, :] · Wp[co, :]ᵀ
 // on the bf16 MFMA GEMM (gemm_bf16.hip, layout 0); dgrad = dy·Wp (layout 1) gathered back by col2im; wgrad =
-// dyᵀ·col (layout 2).  BatchNorm3d (training batch statistics, eps/momentum as nn.BatchNorm3d) is a two-level
-// deterministic column reduction over the [M, C] view plus an apply pass that fuses the residual add and ReLU of
-// torchvision's BasicBlock; its backward fuses the ReLU mask and emits the residual-branch gradient.
-#include "common.h"
+// dyᵀ·col (layout 2).  The channels-last BatchNorm3d, average pool and layout copy that go with them are in
+// bn_cl.hip; the conv epilogues here write the per-tile statistics it combines (channels_last.h has their layout).
+#include "channels_last.h"
 
 namespace {
 
 // Register-prefetched operand loads of padding / out-of-range slots read a valid address and are zeroed when they
 // are written to LDS, not when they are loaded: a select on a prefetched load's result right after the load makes
 // the compiler wait for that load there (s_waitcnt vmcnt(0) in the load phase, before the compute it was meant to
-// overlap).  CMHAR_LATE_ZERO=0 (build flag): the select at the load (A/B builds).
-// s_setprio(1) over a conv kernel's MFMA phase, so a CU's co-resident workgroup in its LDS-store phase does not
-// take issue slots from it (nine-tap forward: R3D-18 layer 2 203.0 -> 196.9 us, layer 3 95.8 -> 92.2, A/B builds)
-#ifndef CMHAR_ROWS3_PRIO
-#define CMHAR_ROWS3_PRIO 1   // conv3d_fwd_rows3
-#endif
-#ifndef CMHAR_ROWS_PRIO
-#define CMHAR_ROWS_PRIO 0    // conv3d_fwd_rows
-#endif
-#ifndef CMHAR_IGEMM_PRIO
-#define CMHAR_IGEMM_PRIO 0   // conv3d_fwd_igemm
-#endif
-#ifndef CMHAR_LATE_ZERO
-#define CMHAR_LATE_ZERO 1
-#endif
-constexpr bool kLateZero = CMHAR_LATE_ZERO != 0;
+// overlap).  (The select at the load was the CMHAR_LATE_ZERO=0 A/B build.)
+// s_setprio(1) over conv3d_fwd_rows3's MFMA phase, so a CU's co-resident workgroup in its LDS-store phase does not
+// take issue slots from it (R3D-18 layer 2 203.0 -> 196.9 us, layer 3 95.8 -> 92.2, A/B builds with
+// CMHAR_ROWS3_PRIO); the same pair over conv3d_fwd_rows and conv3d_fwd_igemm (CMHAR_ROWS_PRIO, CMHAR_IGEMM_PRIO
+// builds) measured within noise, so those kernels run without it.
 __device__ __forceinline__ uint4_t zero_unless(bool ok, uint4_t v) { return ok ? v : uint4_t{0u, 0u, 0u, 0u}; }
 
-template <typename T, int V> __device__ __forceinline__ void vload(const T* p, float* v) {
-  if constexpr (V == 8) Vec8<T>::load(p, v);
-  else for (int j = 0; j < V; ++j) v[j] = to_f<T>(p[j]);
-}
-template <typename T, int V> __device__ __forceinline__ void vstore(T* p, const float* v) {
-  if constexpr (V == 8) Vec8<T>::store(p, v);
-  else for (int j = 0; j < V; ++j) p[j] = from_f<T>(v[j]);
-}
 // conv epilogue output (8 bf16), non-temporal as the GEMM epilogues (R3D-18 step 1659 / 1662 -> 1672 / 1671 clips/s,
-// tools/debug/lib_workload_ab.sh); CMHAR_CONV_NT=0: plain stores
-#ifndef CMHAR_CONV_NT
-#define CMHAR_CONV_NT 1
-#endif
+// tools/debug/lib_workload_ab.sh, against the plain stores of a CMHAR_CONV_NT=0 build)
 __device__ __forceinline__ void zstore8(bf16* p, const float* v) {
-  if (CMHAR_CONV_NT) {
-    bf16x8 r;
+  bf16x8 r;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = (bf16)v[j];
-    typedef int __attribute__((ext_vector_type(4))) i4;
-    __builtin_nontemporal_store(__builtin_bit_cast(i4, r), (i4*)p);
-  } else {
-    Vec8<bf16>::store(p, v);
-  }
+  for (int j = 0; j < 8; ++j) r[j] = (bf16)v[j];
+  typedef int __attribute__((ext_vector_type(4))) i4;
+  __builtin_nontemporal_store(__builtin_bit_cast(i4, r), (i4*)p);
 }
 
 struct Geom {
@@ -245,273 +218,8 @@ __global__ __launch_bounds__(256) void col2im3d_gather(Geom g, const bf16* __res
   }
 }
 
-// ---- BatchNorm over the [M, C] channels-last view ----------------------------------------------------------------
-// Column partial sums over a chunk of rows: each thread reads 8 consecutive channels of a row (one 16-B bf16
-// vector), TPR = C/8 threads cover a row and the block's RPI = 256/TPR row slots are combined in a fixed order.
-// mode 0: Σx; mode 1: Σ(x−mean)²; mode 2: Σg, Σg·x̂ with g = dy·act'(y) (relu 1: [y > 0]; relu 2 = ReLU6:
-// [0 < y < 6]).  part: [2][nchunk][C].  C/8 need not divide 256: the 256 % TPR spare threads only add zeros.
-// relu | BN_ZMASK: the unit had no residual input, so y = act(x̂·w + b) is recomputed from x in bn_cl_apply's exact
-// arithmetic and rounding (bit-identical mask) instead of read: one M×C tensor less per pass.
-constexpr int BN_ZMASK = 4;
-// act'(y) ≠ 0 from the stored y: ReLU [y > 0] (+inf included, as torch's threshold_backward on the result), ReLU6
-// [0 < y < 6]; NaN → 0.
-__device__ __forceinline__ bool bn_y_on(float y, int relu) { return y > 0.f && ((relu & 3) != 2 || y < 6.f); }
-// The same mask from the pre-activation v = fmaf((x − mean)·rstd, w, b) (bn_cl_apply's arithmetic), without the
-// round trip y = T(clamp(v)): for bf16 storage T(v) of 0 < v ≤ 2^-134 is +0 (round to nearest even: 2^-134 is the
-// tie between +0 and the smallest denormal 2^-133) and ReLU6's T(v) reaches 6 from v = 6 − 2^-6 on (the tie rounds
-// to the even 6.0); fp32 storage keeps v.  NaN: the forward's clamp gives 0 → off, as here.
-template <typename T>
-__device__ __forceinline__ bool bn_act_on(float v, int relu) {
-  constexpr bool B16 = sizeof(T) == 2;
-  return v > (B16 ? 0x1p-134f : 0.f) && ((relu & 3) != 2 || v < (B16 ? 5.984375f : 6.f));
-}
-template <typename T, int MODE, bool ZM = false>
-__global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 3) void bn_cl_partial(int M, int C, int rows_per_chunk, const T* __restrict__ x,
-                                                     const T* __restrict__ y, const T* __restrict__ dy,
-                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                     const float* __restrict__ w, const float* __restrict__ b,
-                                                     int relu, float* __restrict__ part) {
-  static_assert(MODE >= 0 && MODE <= 2 && (!ZM || MODE == 2), "modes 0 / 1 / 2; the z-mask in mode 2 only");
-  __shared__ float s0[256][9], s1[256][9];
-  const int tid = threadIdx.x;
-  const int TPR = C / 8, RPI = 256 / TPR;
-  const int slot = tid / TPR, c0 = (tid % TPR) * 8;
-  const int r0 = blockIdx.x * rows_per_chunk;
-  const int r1 = min(r0 + rows_per_chunk, M);
-  const int rs0 = slot < RPI ? r0 + slot : r1;
-  // ZM: a separate instantiation (the mask's w / b and the y loads never share registers); bf16: ≤ 128 VGPRs (launch
-  // bounds), 4 waves per SIMD, the 1024 chunks of bn_chunks in one round; MODE compile-time: one loop body
-  const bool ry = !ZM && MODE == 2 && relu;
-  float mu[8], rs[8], a0[8], a1[8], ww[8], bb[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    mu[j] = MODE ? mean[c0 + j] : 0.f;
-    rs[j] = MODE == 2 ? rstd[c0 + j] : 0.f;
-    ww[j] = ZM ? w[c0 + j] : 0.f;
-    bb[j] = ZM ? b[c0 + j] : 0.f;
-    a0[j] = a1[j] = 0.f;
-  }
-  auto accum = [&](const float* v, const float* gv, const float* yv) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (MODE == 0) {
-        a0[j] += v[j];
-      } else if (MODE == 1) {
-        const float d = v[j] - mu[j];
-        a0[j] = fmaf(d, d, a0[j]);
-      } else {
-        const float xh = (v[j] - mu[j]) * rs[j];
-        const bool off = ZM ? !bn_act_on<T>(fmaf(xh, ww[j], bb[j]), relu) : relu && !bn_y_on(yv[j], relu);
-        const float gj = off ? 0.f : gv[j];
-        a0[j] += gj;
-        a1[j] = fmaf(gj, xh, a1[j]);
-      }
-    }
-  };
-  // four row slots' loads in flight per thread (with 2–3 waves per SIMD one 16-B load per tensor left the kernel at
-  // ~1.5 TB/s), accumulated in the same sequential row order as the one-row tail loop
-  constexpr int UR = 4;
-  int r = rs0;
-  for (; r + (UR - 1) * RPI < r1; r += UR * RPI) {
-    float v[UR][8], gv[UR][8], yv[UR][8];
-#pragma unroll
-    for (int u = 0; u < UR; ++u) {
-      const long off = (long)(r + u * RPI) * C + c0;
-      Vec8<T>::load(x + off, v[u]);
-      if (MODE == 2) {
-        Vec8<T>::load(dy + off, gv[u]);
-        if (ry) Vec8<T>::load(y + off, yv[u]);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < UR; ++u) accum(v[u], gv[u], yv[u]);
-  }
-  for (; r < r1; r += RPI) {
-    const long off = (long)r * C + c0;
-    float v[8], gv[8], yv[8];
-    Vec8<T>::load(x + off, v);
-    if (MODE == 2) {
-      Vec8<T>::load(dy + off, gv);
-      if (ry) Vec8<T>::load(y + off, yv);
-    }
-    accum(v, gv, yv);
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { s0[tid][j] = a0[j]; s1[tid][j] = a1[j]; }
-  __syncthreads();
-  for (int c = tid; c < C; c += 256) {
-    float b0 = 0.f, b1 = 0.f;
-    for (int sl = 0; sl < RPI; ++sl) { b0 += s0[sl * TPR + c / 8][c % 8]; b1 += s1[sl * TPR + c / 8][c % 8]; }
-    part[(long)blockIdx.x * C + c] = b0;
-    if (MODE == 2) part[((long)gridDim.x + blockIdx.x) * C + c] = b1;
-  }
-}
-
-// Combine the chunk partials (BN_FC columns per block, 256 / BN_FC chunk slots, fixed order) and finish the statistic.
-// mode 0: mean;  mode 1: rstd (+ running stats, num_batches_tracked);  mode 2: db = Σg, dw = Σg·x̂.
-// Each slot keeps BN_FU independent partial sums (BN_FU chunk loads in flight instead of one dependent chain; the
-// kernel is load-latency bound: ≤ 512 KiB of partials), combined in a fixed order.
-constexpr int BN_FC = 4, BN_FS = 256 / BN_FC, BN_FU = 4;
-static_assert(BN_FU == 4, "the fixed-order combine below adds four partial sums");
-__global__ __launch_bounds__(256) void bn_cl_final(int mode, long M, int C, int nchunk, const float* __restrict__ part,
-                                                   float* __restrict__ mean, float* __restrict__ rstd,
-                                                   float* __restrict__ rmean, float* __restrict__ rvar,
-                                                   long long* __restrict__ nbt, float momentum, float eps,
-                                                   float* __restrict__ dw, float* __restrict__ db) {
-  __shared__ float s0[256], s1[256];
-  const int tid = threadIdx.x, cl = tid % BN_FC, slot = tid / BN_FC;
-  const int c = blockIdx.x * BN_FC + cl;
-  float a0[BN_FU] = {}, a1[BN_FU] = {};
-  if (c < C) {
-    int k = slot;
-    for (; k + (BN_FU - 1) * BN_FS < nchunk; k += BN_FU * BN_FS) {
-#pragma unroll
-      for (int u = 0; u < BN_FU; ++u) {
-        a0[u] += part[(long)(k + u * BN_FS) * C + c];
-        if (mode == 2) a1[u] += part[((long)nchunk + k + u * BN_FS) * C + c];
-      }
-    }
-    for (; k < nchunk; k += BN_FS) {
-      a0[0] += part[(long)k * C + c];
-      if (mode == 2) a1[0] += part[((long)nchunk + k) * C + c];
-    }
-  }
-  s0[tid] = (a0[0] + a0[1]) + (a0[2] + a0[3]);
-  s1[tid] = (a1[0] + a1[1]) + (a1[2] + a1[3]);
-  __syncthreads();
-  if (slot || c >= C) return;
-  float b0 = 0.f, b1 = 0.f;
-  for (int s = 0; s < BN_FS; ++s) {
-    b0 += s0[s * BN_FC + cl];
-    b1 += s1[s * BN_FC + cl];
-  }
-  if (mode == 0) {
-    mean[c] = b0 / (float)M;
-  } else if (mode == 1) {
-    const float var = b0 / (float)M;
-    rstd[c] = rsqrtf(var + eps);
-    if (rmean) {
-      rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean[c];
-      rvar[c] = (1.f - momentum) * rvar[c] + momentum * var * ((float)M / (float)(M > 1 ? M - 1 : 1));
-    }
-    if (nbt && c == 0) *nbt += 1;
-  } else {
-    db[c] = b0;
-    dw[c] = b1;
-  }
-}
-
-// Combine per-tile (n_t, mean_t, M2_t) over the ntile row tiles written by a conv epilogue (their row counts n_t in
-// `cnt`: 128-row tiles for the generic / 256-row kernels, whole-output-row tiles for the nine-tap forward) with Chan's
-// formula, in a fixed order: mean = Σ n_t·mean_t / M,  M2 = Σ M2_t + n_t·(mean_t − mean)².  Then rstd and the
-// running statistics as bn_cl_final.  Statistics buffer: [2][ntile][C] tile (mean, M2) | [2][ngroup][C] group
-// partials | [ntile] tile counts | [ngroup] group counts (ngroup = ⌈ntile / BN_TG⌉).
-// Level 1: one thread per (group of BN_TG tiles, channel) merges its tiles sequentially (Chan's update) into the
-// group's (mean, M2); channel 0's thread also writes the group's row count.  The group's loads are issued up front
-// (clamped tile index, count 0 past the end) so the sequential merge is not a chain of dependent load latencies.
-constexpr int BN_TG = 16;   // tiles per level-1 group: short sequential chains, enough threads (64 measured 35 us/call)
-__global__ __launch_bounds__(256) void bn_tile_group(int C, int ntile, const float* __restrict__ ts,
-                                                     const float* __restrict__ cnt, float* __restrict__ out,
-                                                     float* __restrict__ gcnt) {
-  const int ngroup = (ntile + BN_TG - 1) / BN_TG;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)ngroup * C) return;
-  const int g = (int)(i / C), c = (int)(i % C);
-  float nv[BN_TG], mv[BN_TG], qv[BN_TG];
-#pragma unroll
-  for (int j = 0; j < BN_TG; ++j) {
-    const int t = min(g * BN_TG + j, ntile - 1);
-    nv[j] = g * BN_TG + j < ntile ? cnt[t] : 0.f;
-    mv[j] = ts[(long)t * C + c];
-    qv[j] = ts[((long)ntile + t) * C + c];
-  }
-  float n = 0.f, mu = 0.f, m2 = 0.f;
-#pragma unroll
-  for (int j = 0; j < BN_TG; ++j) {
-    const float nt = nv[j];
-    if (nt <= 0.f) continue;
-    const float d = mv[j] - mu, n2 = n + nt;
-    mu = fmaf(d, nt / n2, mu);
-    m2 += qv[j] + d * d * (n * nt / n2);
-    n = n2;
-  }
-  out[(long)g * C + c] = mu;
-  out[((long)ngroup + g) * C + c] = m2;
-  if (c == 0) gcnt[g] = n;
-}
-
-// Level 2 over the groups (their row counts in gcnt): BN_GC channels per block, BN_GS group slots, each slot with
-// BN_FU independent partial sums (fixed-order combine).
-constexpr int BN_GC = 4, BN_GS = 256 / BN_GC;
-__global__ __launch_bounds__(256) void bn_tile_final(long M, int C, int ngroup, const float* __restrict__ ts,
-                                                     const float* __restrict__ gcnt, float* __restrict__ mean,
-                                                     float* __restrict__ rstd, float* __restrict__ rmean,
-                                                     float* __restrict__ rvar, long long* __restrict__ nbt,
-                                                     float momentum, float eps) {
-  __shared__ float sh[256];
-  __shared__ float smu[BN_GC];
-  const int tid = threadIdx.x, cl = tid % BN_GC, slot = tid / BN_GC;
-  const int c = blockIdx.x * BN_GC + cl;
-  // pass 1: Σ n_g·mean_g;  pass 2: Σ M2_g + n_g·(mean_g − mean)²
-  auto sweep = [&](bool second, float mu) {
-    float a[BN_FU] = {};
-    if (c < C) {
-      int t = slot;
-      for (; t + (BN_FU - 1) * BN_GS < ngroup; t += BN_FU * BN_GS) {
-#pragma unroll
-        for (int u = 0; u < BN_FU; ++u) {
-          const int tt = t + u * BN_GS;
-          const float m = ts[(long)tt * C + c], n = gcnt[tt];
-          if (second) {
-            const float d = m - mu;
-            a[u] += ts[((long)ngroup + tt) * C + c] + n * d * d;
-          } else {
-            a[u] = fmaf(n, m, a[u]);
-          }
-        }
-      }
-      for (; t < ngroup; t += BN_GS) {
-        const float m = ts[(long)t * C + c], n = gcnt[t];
-        if (second) {
-          const float d = m - mu;
-          a[0] += ts[((long)ngroup + t) * C + c] + n * d * d;
-        } else {
-          a[0] = fmaf(n, m, a[0]);
-        }
-      }
-    }
-    return (a[0] + a[1]) + (a[2] + a[3]);
-  };
-  sh[tid] = sweep(false, 0.f);
-  __syncthreads();
-  if (slot == 0) {
-    float b = 0.f;
-    for (int k = 0; k < BN_GS; ++k) b += sh[k * BN_GC + cl];
-    smu[cl] = b / (float)M;
-  }
-  __syncthreads();
-  const float mu = smu[cl];
-  const float q = sweep(true, mu);
-  __syncthreads();
-  sh[tid] = q;
-  __syncthreads();
-  if (slot || c >= C) return;
-  float m2 = 0.f;
-  for (int k = 0; k < BN_GS; ++k) m2 += sh[k * BN_GC + cl];
-  const float var = m2 / (float)M;
-  mean[c] = mu;
-  rstd[c] = rsqrtf(var + eps);
-  if (rmean) {
-    rmean[c] = (1.f - momentum) * rmean[c] + momentum * mu;
-    rvar[c] = (1.f - momentum) * rvar[c] + momentum * var * ((float)M / (float)(M > 1 ? M - 1 : 1));
-  }
-  if (nbt && c == 0) *nbt += 1;
-}
-
-// Row counts of the tile statistics: where a conv epilogue writes n_t (after the tile and group partials)
-__device__ __forceinline__ float* tile_counts(float* ts, int ntile, int C) {
-  return ts + 2L * (ntile + (ntile + BN_TG - 1) / BN_TG) * C;
-}
+// Row counts of the tile statistics: where a conv epilogue writes n_t
+__device__ __forceinline__ float* tile_counts(float* ts, int ntile, int C) { return ts + tile_stats_layout(ntile, C).cnt; }
 
 // Per-column BatchNorm statistics (mean, Σ(v − mean)²) of the bf16-rounded values of a conv tile's fp32 LDS staging
 // image, by ALL NT threads of the block: ncols (dividing NT) columns, P = NT / ncols row partitions per column (rows
@@ -541,146 +249,6 @@ __device__ __forceinline__ void tile_col_stats(int ncols, float* scr, int tid, V
     float t = 0.f;
     for (int q = 0; q < P; ++q) t += scr[NT + q * ncols + c];
     out(c, mu, t);
-  }
-}
-
-__global__ void bn_cl_eval_stats(int C, const float* __restrict__ rmean, const float* __restrict__ rvar, float eps,
-                                 float* __restrict__ mean, float* __restrict__ rstd) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < C) { mean[c] = rmean[c]; rstd[c] = rsqrtf(rvar[c] + eps); }
-}
-
-// y = act((x − mean)·rstd·w + b + res), act = identity / ReLU (relu 1) / ReLU6 (relu 2), 8 channels per thread.
-// HOIST (C/8 divides 256, so a thread's channels never change along the grid-stride loop): the per-channel
-// constants are loaded once per thread instead of once per vector (8 of the 10 loads of an iteration).
-template <typename T, bool HOIST>
-__global__ __launch_bounds__(256) void bn_cl_apply(unsigned nvec, int C, const T* __restrict__ x,
-                                                   const T* __restrict__ res, const float* __restrict__ mean,
-                                                   const float* __restrict__ rstd, const float* __restrict__ w,
-                                                   const float* __restrict__ b, int relu, T* __restrict__ y) {
-  const unsigned cv = C / 8;
-  float mu[8], rs[8], ww[8], bb[8];
-  // per-channel constants as explicit 16-B loads (c0 % 8 == 0; the per-element form lost its vectorisation
-  // once the activation became a two-way choice: 34 vs 10 loads per 8 channels, 4x slower)
-  auto consts = [&](unsigned i) {
-    const int c0 = (int)(i % cv) * 8;
-    Vec8<float>::load(mean + c0, mu);
-    Vec8<float>::load(rstd + c0, rs);
-    Vec8<float>::load(w + c0, ww);
-    Vec8<float>::load(b + c0, bb);
-  };
-  const unsigned i0 = blockIdx.x * blockDim.x + threadIdx.x;
-  if (HOIST) consts(i0);
-  const float lo = relu ? 0.f : -INFINITY, hi = relu == 2 ? 6.f : INFINITY;
-  for (unsigned i = i0; i < nvec; i += gridDim.x * blockDim.x) {
-    const long off = (long)i * 8;
-    float v[8], rv[8];
-    Vec8<T>::load(x + off, v);
-    if (res) Vec8<T>::load(res + off, rv);
-    if (!HOIST) consts(i);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      v[j] = fmaf((v[j] - mu[j]) * rs[j], ww[j], bb[j]);
-      if (res) v[j] += rv[j];
-      v[j] = fminf(fmaxf(v[j], lo), hi);
-    }
-    Vec8<T>::store(y + off, v);
-  }
-}
-
-// g = dy·act'(y);  dres = g (optional);  dx = w·rstd·(g − Σg/M − x̂·Σgx̂/M) (training) or w·rstd·g (eval).
-// relu | BN_ZMASK: act'(y) recomputed from x (no residual; see bn_cl_partial), y not read.  HOIST: as bn_cl_apply.
-template <typename T, bool HOIST>
-__global__ __launch_bounds__(256) void bn_cl_bwd_apply(unsigned nvec, int M, int C, const T* __restrict__ x,
-                                                       const T* __restrict__ y, const T* __restrict__ dy,
-                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                       const float* __restrict__ w, const float* __restrict__ b,
-                                                       const float* __restrict__ dw, const float* __restrict__ db,
-                                                       int training, int relu, T* __restrict__ dx,
-                                                       T* __restrict__ dres) {
-  const float inv = 1.f / (float)M;
-  const unsigned cv = C / 8;
-  const bool zm = relu & BN_ZMASK, ry = relu && !zm, needx = training || zm;
-  float rs[8], ww[8], mu[8], sw[8], sb[8], bb[8];
-  // per-channel constants as explicit 16-B loads (c0 % 8 == 0): per element they compiled to 40 scalar loads
-  auto consts = [&](unsigned i) {
-    const int c0 = (int)(i % cv) * 8;
-    Vec8<float>::load(rstd + c0, rs);
-    Vec8<float>::load(w + c0, ww);
-    if (needx) Vec8<float>::load(mean + c0, mu);
-    if (training) {
-      Vec8<float>::load(dw + c0, sw);
-      Vec8<float>::load(db + c0, sb);
-    }
-    if (zm) Vec8<float>::load(b + c0, bb);
-  };
-  const unsigned i0 = blockIdx.x * blockDim.x + threadIdx.x;
-  if (HOIST) consts(i0);
-  for (unsigned i = i0; i < nvec; i += gridDim.x * blockDim.x) {
-    const long off = (long)i * 8;
-    float gv[8], yv[8], xv[8], out[8];
-    Vec8<T>::load(dy + off, gv);
-    if (ry) Vec8<T>::load(y + off, yv);
-    if (needx) Vec8<T>::load(x + off, xv);
-    if (!HOIST) consts(i);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (zm ? !bn_act_on<T>(fmaf((xv[j] - mu[j]) * rs[j], ww[j], bb[j]), relu) : ry && !bn_y_on(yv[j], relu))
-        gv[j] = 0.f;
-      if (training) {
-        const float xh = (xv[j] - mu[j]) * rs[j];
-        out[j] = ww[j] * rs[j] * (gv[j] - sb[j] * inv - xh * sw[j] * inv);
-      } else {
-        out[j] = ww[j] * rs[j] * gv[j];
-      }
-    }
-    if (dres) Vec8<T>::store(dres + off, gv);
-    Vec8<T>::store(dx + off, out);
-  }
-}
-
-// Global average pool over the S positions of each clip: [N, S, C] → fp32 [N, C]; backward broadcasts dout/S.
-template <typename T>
-__global__ __launch_bounds__(256) void avgpool_cl_fwd(int N, long S, int C, const T* __restrict__ x,
-                                                      float* __restrict__ out) {
-  __shared__ float sh[256];
-  const int n = blockIdx.y, tid = threadIdx.x;
-  const int CB = C < 256 ? C : 256, RPI = 256 / CB, slot = tid / CB, cc = tid % CB;
-  for (int c0 = blockIdx.x * CB; c0 < C; c0 += gridDim.x * CB) {
-    float a = 0.f;
-    if (slot < RPI && c0 + cc < C)      // (C not a multiple of CB / CB not dividing 256: spare threads add 0)
-      for (long s = slot; s < S; s += RPI) a += to_f<T>(x[((long)n * S + s) * C + c0 + cc]);
-    sh[tid] = a;
-    __syncthreads();
-    if (slot == 0 && c0 + cc < C) {
-      float b = 0.f;
-      for (int k = 0; k < RPI; ++k) b += sh[k * CB + cc];
-      out[(long)n * C + c0 + cc] = b / (float)S;
-    }
-    __syncthreads();
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void avgpool_cl_bwd(long total, long S, int C, const float* __restrict__ dout,
-                                                      T* __restrict__ dx) {
-  const float inv = 1.f / (float)S;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C);
-    const long n = i / C / S;
-    dx[i] = from_f<T>(dout[n * C + c] * inv);
-  }
-}
-
-// (B, T, C, H, W) fp32 video → (B, T, H, W, C) compute dtype.
-template <typename T>
-__global__ __launch_bounds__(256) void video_ndhwc_kernel(long total, int C, long HW, const float* __restrict__ v,
-                                                          T* __restrict__ out) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C);
-    const long p = i / C;          // (b·T + t)·HW + hw
-    const long bt = p / HW, hw = p - bt * HW;
-    out[i] = from_f<T>(v[(bt * C + c) * HW + hw]);
   }
 }
 
@@ -871,9 +439,7 @@ __global__ __launch_bounds__(256, JN == 2 ? 3 : 2) void conv3d_fwd_igemm(Geom g,
     const int cur = (kt - kb) & 1;
     const bool more = kt + 1 < ke;
     if (more) load((kt + 1) * BK);
-    if (CMHAR_IGEMM_PRIO) __builtin_amdgcn_s_setprio(1);
     mma_tile<true, true, JN>(smem + 16384 * cur, smem + Lds::B0 + Lds::BSTAGE * cur, wr, wc, lane, acc);
-    if (CMHAR_IGEMM_PRIO) __builtin_amdgcn_s_setprio(0);
     if (more) store(cur ^ 1);
     __syncthreads();
   }
@@ -1161,28 +727,24 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3d_wgrad_rows(Geom g, int Cout
 namespace wr3 {
 constexpr int SLOTS = 256, SQ = 352, RS = 144;
 constexpr int DZB = SLOTS * RS, DZ_N = SLOTS * 8;
-// CS = input channels per workgroup: 64 (one 12-wave workgroup per CU, 36 column blocks) or 32 (CMHAR_WGRAD3_CS=32:
-// two 6-wave workgroups per CU, 18 column blocks each, 80-B slab rows — each stages the dz chunk itself, and the two
-// run out of phase, one's LDS stores and barriers beside the other's MFMAs).  Round 6 (168 VGPRs,
-// 65 KB LDS, R3D tests green): layer 1 / 2 / 3 weight gradients 405.7 / 207.5 / 114.3 -> 524.9 / 288.7 / 154.5 us,
-// the R3D-18 step 2218 / 2253 -> 2192 / 2167 clips/s — the duplicated dz staging costs more than the overlap wins; 64)
-template <int CS> struct C3 {
-  static constexpr int NW = CS == 64 ? 12 : 6, NT = 64 * NW, CPT = CS / 16, NCB = 9 * CPT;
-  static constexpr int SLC = CS / 8, RSL = CS * 2 + 16;               // 16-B chunks per slab slot, slab row bytes
-  static constexpr int SLB = SQ * RSL, SL_N = SQ * SLC;
-  static constexpr int DZ_PER = (DZ_N + NT - 1) / NT, SL_PER = (SL_N + NT - 1) / NT;
-  static_assert(NCB == 3 * NW, "three column blocks per wave");
-};
+// CS = input channels per workgroup: 64 (one 12-wave workgroup per CU, 36 column blocks).  A 32-channel form was
+// measured in round 6 with CMHAR_WGRAD3_CS=32 (two 6-wave workgroups per CU, 18 column blocks each, 80-B slab rows —
+// each staged the dz chunk itself, and the two ran out of phase, one's LDS stores and barriers beside the other's
+// MFMAs; 168 VGPRs, 65 KB LDS, R3D tests green): layer 1 / 2 / 3 weight gradients 405.7 / 207.5 /
+// 114.3 -> 524.9 / 288.7 / 154.5 us, the R3D-18 step 2218 / 2253 -> 2192 / 2167 clips/s — the duplicated dz staging
+// cost more than the overlap won, and that instance is gone.
+constexpr int CS = 64, NW = 12, NT = 64 * NW, CPT = CS / 16, NCB = 9 * CPT;
+constexpr int SLC = CS / 8, RSL = CS * 2 + 16;                        // 16-B chunks per slab slot, slab row bytes
+constexpr int SLB = SQ * RSL, SL_N = SQ * SLC;
+constexpr int DZ_PER = (DZ_N + NT - 1) / NT, SL_PER = (SL_N + NT - 1) / NT;
+static_assert(NCB == 3 * NW, "three column blocks per wave");
 }  // namespace wr3
 
-template <int CS>
-__global__ __launch_bounds__(wr3::C3<CS>::NT, CS == 64 ? 1 : 2) void conv3d_wgrad_rows3(
+__global__ __launch_bounds__(wr3::NT, 1) void conv3d_wgrad_rows3(
     Geom g, int Cout, int R, int Ls, int cpf, int nchunk, int chunks_per_split, const bf16* __restrict__ x,
     const bf16* __restrict__ dz, float* __restrict__ out) {
   using namespace wr3;
-  typedef C3<CS> Q;
-  constexpr int NT = Q::NT, RSL = Q::RSL, SLC = Q::SLC, CPT = Q::CPT, DZ_PER = Q::DZ_PER, SL_PER = Q::SL_PER;
-  __shared__ __attribute__((aligned(16))) char smem[DZB + Q::SLB];
+  __shared__ __attribute__((aligned(16))) char smem[DZB + SLB];
   char* const dzs = smem;
   char* const sls = smem + DZB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1256,7 +818,7 @@ __global__ __launch_bounds__(wr3::C3<CS>::NT, CS == 64 ? 1 : 2) void conv3d_wgra
 #pragma unroll
     for (int i = 0; i < SL_PER; ++i) {
       const int e = i * NT + tid;
-      if (e < Q::SL_N) *(uint4_t*)(sls + (e / SLC) * RSL + (e % SLC) * 16) = rsl[i];
+      if (e < SL_N) *(uint4_t*)(sls + (e / SLC) * RSL + (e % SLC) * 16) = rsl[i];
     }
   };
   floatx4 acc[4][3];
@@ -1444,7 +1006,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_rows(Geom g, int M, int Cou
   for (int ks = ks0; ks < nks; ++ks) {
     const bool more = ks + 1 < nks;
     if (more) load(ks + 1);
-    if (CMHAR_ROWS_PRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int iw = 0; iw < 3; ++iw)
 #pragma unroll
@@ -1460,7 +1021,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_rows(Geom g, int M, int Cou
 #pragma unroll
           for (int j = 0; j < JB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
       }
-    if (CMHAR_ROWS_PRIO) __builtin_amdgcn_s_setprio(0);
     __syncthreads();
     if (more) store();
     __syncthreads();
@@ -1553,31 +1113,30 @@ __global__ __launch_bounds__(256) void conv_split_reduce(int M, int Cout, int ns
 // another (slab kept), so each staged input byte feeds 3·3 taps instead of 3 (the 256-row kernel restages per ih).
 // Same 4-wave 64-slot x 64-Cout layout and register prefetch as conv3d_fwd_rows<256>; BatchNorm statistics per
 // frame tile (its row count written by the first Cout slice).
-// LDS images (SW): unpadded 128-B rows with the 16-B chunk c of row r stored at chunk (c ^ r) & 7.  The A fragment
+// LDS images: unpadded 128-B rows with the 16-B chunk c of row r stored at chunk (c ^ r) & 7.  The A fragment
 // read (ds_read_b128: lanes 16 consecutive slab rows x 4 chunks, lane groups {0-3,12-15,20-27}, ... of
 // MI355X_MICROARCH.md §LDS, bank (a/4) % 64) is then conflict-free when its 16 rows are consecutive and 2-way where
 // they straddle an output row (the slab skips Ls - Wo = 2 rows there); the weight reads are conflict-free.  The
-// 144-B padded rows (SW = false, CMHAR_ROWS3_SWZ=0) are 2-way on every A and B read and 2.5-3-way at row seams
-// (2.4x the LDS read cycles; PMC: 55 bank-conflict cycles per 131 LDS-array cycles, gpurun_out/s2c_pmc_conv.txt).
+// 144-B padded rows this replaced (the CMHAR_ROWS3_SWZ=0 arm of the A/B) were 2-way on every A and B read and
+// 2.5-3-way at row seams (2.4x the LDS read cycles; PMC: 55 bank-conflict cycles per 131 LDS-array cycles).
 namespace fr3 {
-constexpr int SQ = 352, TN = 64, NT = 256, RS = 144, ELD = TN + 4;
+constexpr int SQ = 352, TN = 64, NT = 256, ELD = TN + 4;
 constexpr int SL_PER = (SQ * 8 + NT - 1) / NT, W_PER = 3 * TN * 8 / NT;
-template <bool SW> struct L {
-  static constexpr int RB = SW ? 128 : RS;                       // bytes per LDS row
+struct L {
+  static constexpr int RB = 128;                                   // bytes per LDS row
   static constexpr int SLAB = SQ * RB, WB = 3 * TN * RB, EPI = 256 * ELD * 4 + 2048;
   static constexpr int BYTES = SLAB + WB > EPI ? SLAB + WB : EPI;  // epilogue staging + statistics scratch overlay
   // byte offset of 16-B chunk c of row r
-  static __device__ __forceinline__ int at(int r, int c) { return SW ? (r << 7) | (((r ^ c) & 7) << 4) : r * RS + c * 16; }
+  static __device__ __forceinline__ int at(int r, int c) { return (r << 7) | (((r ^ c) & 7) << 4); }
 };
 }  // namespace fr3
 
-template <bool SW>
 __global__ __launch_bounds__(256, 2) void conv3d_fwd_rows3(Geom g, int Cout, int R, int Ls, int cpf,
                                                            const bf16* __restrict__ x, const bf16* __restrict__ Wt,
                                                            const bf16* __restrict__ res, bf16* __restrict__ z,
                                                            float* __restrict__ tstats) {
   using namespace fr3;
-  typedef fr3::L<SW> LY;
+  typedef fr3::L LY;
   __shared__ __attribute__((aligned(16))) char smem[LY::BYTES];
   char* const slab = smem;
   char* const wl = smem + LY::SLAB;
@@ -1671,14 +1230,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_rows3(Geom g, int Cout, int
       for (int kk = 0; kk < 2; ++kk) {
         bf16x8 af[4], bfr[4];
         // K half kk = chunks 4kk..4kk+3: chunk bit 2, i.e. byte-offset bit 6 of the swizzled address (rows are
-        // 128 B, the XOR key only touches bits 4-6), or + 64 B on the padded rows
+        // 128 B, the XOR key only touches bits 4-6)
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-          af[i] = *(const bf16x8*)(slab + (SW ? LY::at(a_row[i] + rsh + iw, cl) ^ (kk << 6)
-                                               : LY::at(a_row[i] + rsh + iw, cl) + kk * 64));
+        for (int i = 0; i < 4; ++i) af[i] = *(const bf16x8*)(slab + (LY::at(a_row[i] + rsh + iw, cl) ^ (kk << 6)));
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-          bfr[j] = *(const bf16x8*)(wl + (iw * TN + 16 * j) * LY::RB + (SW ? b_off ^ (kk << 6) : b_off + kk * 64));
+        for (int j = 0; j < 4; ++j) bfr[j] = *(const bf16x8*)(wl + (iw * TN + 16 * j) * LY::RB + (b_off ^ (kk << 6)));
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1699,9 +1255,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_rows3(Geom g, int Cout, int
       if ((st + 1) % 3 == 0) load_slab((st + 1) / 3);
       load_w(st + 1);
     }
-    if (CMHAR_ROWS3_PRIO) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
     compute(st % 3);
-    if (CMHAR_ROWS3_PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     __syncthreads();
     if (more) {
       if ((st + 1) % 3 == 0) store_slab();
@@ -2018,20 +1574,6 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_reduce(long n4, int splits, 
   }
 }
 
-inline int grid_for(long work) {
-  const long b = (work + 255) / 256;
-  return (int)(b < 8192 ? (b > 0 ? b : 1) : 8192);
-}
-
-inline bool bn_channels_ok(int C) { return C >= 8 && C % 8 == 0 && C <= 2048; }
-
-// ≤ 1024 chunks of ≥ 16 K elements per tensor: four blocks per CU stream the big R3D-18 layers (M·C = 103 M at
-// 16×56², where ≤ 512 chunks of ≥ 512 rows ran 1.5 TB/s), a few blocks the 7² layer-4 maps; few partials to combine
-inline int bn_chunks(long M, int C) {
-  const long c = (M * C + 16383) / 16384;
-  return (int)(c < 1024 ? (c > 0 ? c : 1) : 1024);
-}
-
 Geom make_geom(const int* dims) {
   Geom g;
   g.N = dims[0]; g.T = dims[1]; g.H = dims[2]; g.W = dims[3]; g.C = dims[4];
@@ -2110,381 +1652,174 @@ extern "C" int cmhar_conv3d_col2im(int dtype, const int* dims, const void* dcol,
   return 0;
 }
 
-// A thread's 8 channels are fixed along the grid-stride loop when C/8 divides 256 (grid_for's blocks are 256 wide)
-inline bool bn_hoist(int C) { return 256 % (C / 8) == 0; }
-
-template <typename T>
-void bn_apply_launch(long M, int C, const void* x, const void* res, const float* smean, const float* srstd,
-                     const float* w, const float* b, int relu, void* y, hipStream_t stream) {
-  const unsigned nvec = (unsigned)(M * C / 8);
-  if (bn_hoist(C))
-    bn_cl_apply<T, true><<<grid_for(nvec), 256, 0, stream>>>(nvec, C, (const T*)x, (const T*)res, smean, srstd, w,
-                                                              b, relu, (T*)y);
-  else
-    bn_cl_apply<T, false><<<grid_for(nvec), 256, 0, stream>>>(nvec, C, (const T*)x, (const T*)res, smean, srstd, w,
-                                                               b, relu, (T*)y);
-}
-
-// BatchNorm backward: column partials (Σg, Σg·x̂), their combination into db / dw, then dx (and dres).
-// y == nullptr with relu != 0: no residual entered the unit, the activation mask is recomputed from x (BN_ZMASK).
-template <typename T>
-int bn_bwd_launch(long M, int C, const void* x, const void* y, const void* dy, const float* w, const float* b,
-                  const float* smean, const float* srstd, void* dx, void* dres, float* dw, float* db, int training,
-                  int relu, float* ws, hipStream_t stream) {
-  const int nch = bn_chunks(M, C);
-  const int rpc = (int)((M + nch - 1) / nch);
-  const int act = relu && !y ? relu | BN_ZMASK : relu;
-  if (act & BN_ZMASK)
-    bn_cl_partial<T, 2, true><<<nch, 256, 0, stream>>>((int)M, C, rpc, (const T*)x, (const T*)y, (const T*)dy, smean,
-                                                     srstd, w, b, act, ws);
-  else
-    bn_cl_partial<T, 2, false><<<nch, 256, 0, stream>>>((int)M, C, rpc, (const T*)x, (const T*)y, (const T*)dy,
-                                                      smean, srstd, w, b, act, ws);
-  bn_cl_final<<<(C + BN_FC - 1) / BN_FC, 256, 0, stream>>>(2, M, C, nch, ws, nullptr, nullptr, nullptr, nullptr,
-                                                           nullptr, 0.f, 0.f, dw, db);
-  const unsigned nvec = (unsigned)(M * C / 8);
-  if (bn_hoist(C))
-    bn_cl_bwd_apply<T, true><<<grid_for(nvec), 256, 0, stream>>>(nvec, (int)M, C, (const T*)x, (const T*)y,
-                                                                  (const T*)dy, smean, srstd, w, b, dw, db, training,
-                                                                  act, (T*)dx, (T*)dres);
-  else
-    bn_cl_bwd_apply<T, false><<<grid_for(nvec), 256, 0, stream>>>(nvec, (int)M, C, (const T*)x, (const T*)y,
-                                                                   (const T*)dy, smean, srstd, w, b, dw, db, training,
-                                                                   act, (T*)dx, (T*)dres);
-  return 0;
-}
-
-extern "C" long cmhar_bn_cl_ws(long M, int C) { return 2L * bn_chunks(M, C) * C; }
-
-extern "C" int cmhar_bn_cl_fwd(int dtype, long M, int C, const void* x, const void* res, void* y, const float* w,
-                               const float* b, float* rmean, float* rvar, float* smean, float* srstd, int training,
-                               float momentum, float eps, int relu, long long* num_batches_tracked, float* ws,
-                               hipStream_t stream) {
-  if (M <= 0 || !bn_channels_ok(C) || !ws) return -1;
-  if (M >= (1L << 31) || M * C / 8 >= (1L << 31)) return -2;   // unsigned grid-stride loops never wrap
-  const int nch = bn_chunks(M, C);
-  const int rpc = (int)((M + nch - 1) / nch);
-  const int fgrid = (C + BN_FC - 1) / BN_FC;
-  if (training) {
-    for (int mode = 0; mode < 2; ++mode) {
-#define BNP(T, MODE)                                                                                            \
-  bn_cl_partial<T, MODE><<<nch, 256, 0, stream>>>((int)M, C, rpc, (const T*)x, nullptr, nullptr, smean, nullptr,  \
-                                                  nullptr, nullptr, 0, ws)
-      if (dtype == CMHAR_BF16) {
-        if (mode == 0) BNP(bf16, 0);
-        else BNP(bf16, 1);
-      } else if (dtype == CMHAR_F32) {
-        if (mode == 0) BNP(float, 0);
-        else BNP(float, 1);
-      } else return -1;
-#undef BNP
-      bn_cl_final<<<fgrid, 256, 0, stream>>>(mode, M, C, nch, ws, smean, srstd, rmean, rvar, num_batches_tracked,
-                                             momentum, eps, nullptr, nullptr);
-    }
-  } else {
-    if (!rmean || !rvar) return -2;
-    bn_cl_eval_stats<<<(C + 255) / 256, 256, 0, stream>>>(C, rmean, rvar, eps, smean, srstd);
-  }
-  if (dtype == CMHAR_BF16) bn_apply_launch<bf16>(M, C, x, res, smean, srstd, w, b, relu, y, stream);
-  else bn_apply_launch<float>(M, C, x, res, smean, srstd, w, b, relu, y, stream);
-  CMHAR_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int cmhar_bn_cl_fwd_tiles(long M, int C, int ntile, float* tile_stats, const void* x, const void* res,
-                                     void* y, const float* w, const float* b, float* rmean, float* rvar,
-                                     float* smean, float* srstd, float momentum, float eps, int relu,
-                                     long long* num_batches_tracked, hipStream_t stream) {
-  if (M <= 0 || !bn_channels_ok(C) || !tile_stats || ntile <= 0) return -1;
-  if (M >= (1L << 31) || M * C / 8 >= (1L << 31)) return -2;   // unsigned grid-stride loops never wrap
-  const int ngroup = (ntile + BN_TG - 1) / BN_TG;
-  float* groups = (float*)tile_stats + 2L * ntile * C;
-  const float* cnt = (float*)tile_stats + 2L * (ntile + ngroup) * C;
-  float* gcnt = (float*)cnt + ntile;
-  bn_tile_group<<<cdiv((long)ngroup * C, 256), 256, 0, stream>>>(C, ntile, tile_stats, cnt, groups, gcnt);
-  bn_tile_final<<<(C + BN_GC - 1) / BN_GC, 256, 0, stream>>>(M, C, ngroup, groups, gcnt, smean, srstd, rmean, rvar,
-                                                   num_batches_tracked, momentum, eps);
-  bn_apply_launch<bf16>(M, C, x, res, smean, srstd, w, b, relu, y, stream);
-  CMHAR_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int cmhar_bn_cl_bwd(int dtype, long M, int C, const void* x, const void* y, const void* dy,
-                               const float* w, const float* smean, const float* srstd, void* dx, void* dres,
-                               float* dw, float* db, int training, int relu, float* ws, hipStream_t stream) {
-  if (M <= 0 || !bn_channels_ok(C) || !ws || !dw || !db || (relu && !y)) return -1;
-  if (M >= (1L << 31) || M * C / 8 >= (1L << 31)) return -2;   // unsigned grid-stride loops never wrap
-  if (dtype == CMHAR_BF16)
-    bn_bwd_launch<bf16>(M, C, x, y, dy, w, nullptr, smean, srstd, dx, dres, dw, db, training, relu, ws, stream);
-  else if (dtype == CMHAR_F32)
-    bn_bwd_launch<float>(M, C, x, y, dy, w, nullptr, smean, srstd, dx, dres, dw, db, training, relu, ws, stream);
-  else return -1;
-  CMHAR_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int cmhar_bn_cl_bwd_nores(int dtype, long M, int C, const void* x, const void* dy, const float* w,
-                                     const float* b, const float* smean, const float* srstd, void* dx, float* dw,
-                                     float* db, int training, int relu, float* ws, hipStream_t stream) {
-  if (M <= 0 || !bn_channels_ok(C) || !ws || !dw || !db || relu < 0 || relu > 2 || (relu && !b)) return -1;
-  if (M >= (1L << 31) || M * C / 8 >= (1L << 31)) return -2;   // unsigned grid-stride loops never wrap
-  if (dtype == CMHAR_BF16)
-    bn_bwd_launch<bf16>(M, C, x, nullptr, dy, w, b, smean, srstd, dx, nullptr, dw, db, training, relu, ws, stream);
-  else if (dtype == CMHAR_F32)
-    bn_bwd_launch<float>(M, C, x, nullptr, dy, w, b, smean, srstd, dx, nullptr, dw, db, training, relu, ws, stream);
-  else return -1;
-  CMHAR_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int cmhar_avgpool_cl(int dtype, int N, long S, int C, const void* x, float* out, hipStream_t stream) {
-  if (N <= 0 || S <= 0 || !bn_channels_ok(C)) return -1;
-  const int CB = C < 256 ? C : 256;
-  dim3 grid(cdiv(C, CB), N);
-  if (dtype == CMHAR_BF16) avgpool_cl_fwd<bf16><<<grid, 256, 0, stream>>>(N, S, C, (const bf16*)x, out);
-  else if (dtype == CMHAR_F32) avgpool_cl_fwd<float><<<grid, 256, 0, stream>>>(N, S, C, (const float*)x, out);
-  else return -1;
-  CMHAR_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int cmhar_avgpool_cl_bwd(int dtype, int N, long S, int C, const float* dout, void* dx,
-                                    hipStream_t stream) {
-  if (N <= 0 || S <= 0 || C <= 0) return -1;
-  const long total = (long)N * S * C;
-  if (dtype == CMHAR_BF16) avgpool_cl_bwd<bf16><<<grid_for(total), 256, 0, stream>>>(total, S, C, dout, (bf16*)dx);
-  else if (dtype == CMHAR_F32)
-    avgpool_cl_bwd<float><<<grid_for(total), 256, 0, stream>>>(total, S, C, dout, (float*)dx);
-  else return -1;
-  CMHAR_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int cmhar_video_to_ndhwc(int out_dtype, int B, int T, int C, int H, int W, const float* video, void* out,
-                                    hipStream_t stream) {
-  if (B <= 0 || T <= 0 || C <= 0 || H <= 0 || W <= 0) return -1;
-  const long total = (long)B * T * C * H * W, HW = (long)H * W;
-  if (out_dtype == CMHAR_BF16)
-    video_ndhwc_kernel<bf16><<<grid_for(total), 256, 0, stream>>>(total, C, HW, video, (bf16*)out);
-  else if (out_dtype == CMHAR_F32)
-    video_ndhwc_kernel<float><<<grid_for(total), 256, 0, stream>>>(total, C, HW, video, (float*)out);
-  else return -1;
-  CMHAR_CHECK_LAUNCH();
-  return 0;
-}
-
 // ---- implicit-GEMM entry points (bf16, C % 64 == 0, Kp == kt·kh·kw·C) ----
 static bool igemm_ok(const Geom& g, int Cout) {
   return geom_ok(g) && g.C % 64 == 0 && g.Kp == g.K && Cout > 0 && Cout % 8 == 0 &&
          (long)g.N * g.To * g.Ho * g.Wo < (1L << 31);
 }
 
-// Statistics tiles the forward plan writes (see cmhar_conv3d_fwd; all its kernels use 128-row tiles) and the floats
-// the caller provides for them: tile and group partials plus their row counts.
-// Nine-tap forward (conv3d_fwd_rows3) plan: Cout % 64 == 0, 3x3 taps at unit H/W stride, R + 2 input rows of a
-// tile in the slab, R = ⌈Ho / cpf⌉ with cpf = ⌈Ho / ⌊256 / Wo⌋⌉ tiles per frame (balanced: R3D-18 layer 2 takes
-// 4 x 7 rows, not 9 + 9 + 9 + 1), and at least 3/4 of the tile's 256 MFMA row slots used (layer 4's 7 x 7 frames
-// would use 49: it keeps the split-K row-slab kernel).  ntile counts frame tiles; the grid is ntile x Cout / 64.
-// CMHAR_FWD_ROWS3=0 turns it off, =1 keeps it to Cout = 64 (R3D-18 layer 1 only; A/B runs).
-struct Fwd3Plan { int R, Ls, cpf, ntile; };
-static bool fwd3_plan(const Geom& g, int Cout, Fwd3Plan& p) {
-  static const int mode = [] {
-    const char* v = getenv("CMHAR_FWD_ROWS3");
-    return v && (v[0] == '0' || v[0] == '1') ? v[0] - '0' : 2;
-  }();
-  if (!mode || (mode == 1 && Cout != fr3::TN) || Cout % fr3::TN || g.kh != 3 || g.kw != 3 || g.sh != 1 ||
-      g.sw != 1 || g.C % 64 || g.Wo > 256 || (long)g.N * g.T * g.H * g.W * g.C * 2 > (1L << 30) ||
-      (long)Cout * g.Kp * 2 > 0x7fffffffL)   // 32-bit buffer offsets of x (<= 1 GiB) and of the weights
-    return false;
-  const int r0 = min(256 / g.Wo, g.Ho);
-  p.cpf = (g.Ho + r0 - 1) / r0;
-  p.R = (g.Ho + p.cpf - 1) / p.cpf;
-  p.Ls = g.Wo - 1 + g.kw;
-  if ((p.R + 2) * p.Ls > fr3::SQ || 4 * p.R * g.Wo < 3 * 256 || (p.cpf - 1) * p.R >= g.Ho) return false;
-  p.ntile = g.N * g.To * p.cpf;
-  return true;
+// Everything cmhar_conv3d_fwd, cmhar_conv3d_fwd_split and the queries beside them need, decided once.
+//
+// arm (exported as cmhar_conv3d_fwd_plan so tests pin the kernel a geometry takes): 1 = nine-tap conv3d_fwd_rows3,
+// 2 = row-slab conv3d_fwd_rows<128>, 3 = row-slab conv3d_fwd_rows<256>, 4 = generic conv3d_fwd_igemm 128x64,
+// 5 = generic conv3d_fwd_igemm 128x128; -1 = not an implicit-GEMM geometry.  Each arm was once behind a switch
+// (CMHAR_FWD_ROWS3, CMHAR_FWD_ROWS, CMHAR_FWD_SPLIT); the A/B runs they served are recorded below and in DESIGN.md.
+//
+// Nine-tap forward (arm 1): Cout % 64 == 0, 3x3 taps at unit H/W stride, R + 2 input rows of a tile in the slab,
+// R = ⌈Ho / cpf⌉ with cpf = ⌈Ho / ⌊256 / Wo⌋⌉ tiles per frame (balanced: R3D-18 layer 2 takes 4 x 7 rows, not
+// 9 + 9 + 9 + 1), and at least 3/4 of the tile's 256 MFMA row slots used (layer 4's 7 x 7 frames would use 49: it
+// keeps the split-K row-slab kernel).  Its statistics tiles are the frame tiles; the grid is stat_tiles x Cout / 64.
+// Every other arm writes statistics per 128 rows.
+//
+// Split-K (splits > 0, the caller's choice: cmhar_conv3d_fwd_split_ws > 0) for the forward convs whose 128-row tile
+// grid leaves most of the chip idle (R3D-18 layer 4: 3136 rows × 512 outputs = 200 tiles for 512 workgroup slots):
+// the (it, ih, channel-slice) K-steps of conv3d_fwd_rows<128> split over `splits` workgroups per tile, fp32 partials
+// in the caller's workspace, conv_split_reduce sums them in order (+ residual) and rounds once.  No BatchNorm tile
+// statistics (the caller takes the statistics passes over z: small at these sizes).  The generic implicit GEMM
+// (strided convs: R3D-18 layer 4's stride-2 3x3 conv, 3136 x 512 = 100 128x128 tiles, and its 1x1 downsample)
+// splits the same way over its BK-wide K-steps, kps of them per split, in its buffer-resource instantiation only.
+struct FwdPlan {
+  int arm = -1;
+  int M = 0, Ls = 0;
+  int R = 0, cpf = 0;         // arm 1: output rows per tile, tiles per frame
+  bool buf = false;           // arms 4 / 5: 32-bit buffer offsets (x and the weights under 2 GiB)
+  int grid = 0;               // workgroups of one split (blockIdx.x)
+  int splits = 0, kps = 0;    // split-K: 0 = unsplit; arms 4 / 5: K-steps per split
+  int stat_tiles = 0;
+};
+static FwdPlan plan_fwd(const Geom& g, int Cout) {
+  FwdPlan p;
+  if (!igemm_ok(g, Cout)) return p;
+  p.M = g.N * g.To * g.Ho * g.Wo;
+  p.Ls = (g.Wo - 1) * g.sw + g.kw;
+  const long xbytes = (long)g.N * g.T * g.H * g.W * g.C * 2, wbytes = (long)Cout * g.Kp * 2;
+  const int tiles128 = (p.M + 127) / 128;
+  p.stat_tiles = tiles128;
+  // the slab kernels' 32-bit buffer offsets: x within 1 GiB, the weights within 2 GiB
+  const bool slab = g.kw == 3 && Cout % fr::TN == 0 && xbytes <= (1L << 30) && wbytes <= 0x7fffffffL;
+  if (slab && g.kh == 3 && g.sh == 1 && g.sw == 1 && g.Wo <= 256) {
+    const int r0 = min(256 / g.Wo, g.Ho);
+    const int cpf = (g.Ho + r0 - 1) / r0, R = (g.Ho + cpf - 1) / cpf;
+    if ((R + 2) * p.Ls <= fr3::SQ && 4 * R * g.Wo >= 3 * 256 && (cpf - 1) * R < g.Ho) {
+      p.arm = 1;
+      p.R = R;
+      p.cpf = cpf;
+      p.stat_tiles = g.N * g.To * cpf;
+      p.grid = p.stat_tiles * (Cout / fr3::TN);
+      return p;
+    }
+  }
+  const long t256 = (long)((p.M + 255) / 256) * (Cout / fr::TN);
+  if (slab && g.Wo <= 255 && p.Ls <= 255) {
+    auto fits = [&](int tm, int sq) { return (long)((tm + g.Wo - 2) / g.Wo + 1) * p.Ls <= sq; };   // rows a tile touches
+    // 256-row tiles while they give every CU a workgroup, else 128-row tiles (R3D-18 layer 4: 268 -> 164 us; layer 3
+    // at 392 256-row tiles measured 167 vs 199 us, so it keeps them)
+    if (t256 < 256 && fits(128, fr::Cfg<128>::SQ)) p.arm = 2;
+    else if (fits(256, fr::Cfg<256>::SQ)) p.arm = 3;
+  }
+  if (p.arm == 2) {
+    const long t128 = (long)tiles128 * (Cout / fr::TN);
+    p.grid = (int)t128;
+    const int nks = g.kt * g.kh * (g.C / 64);
+    const int s = (int)std::min<long>(4, (512 + t128 - 1) / t128);
+    if (t128 < 256 && s >= 2 && nks >= 2 * s) p.splits = s;
+  } else if (p.arm == 3) {
+    p.grid = (int)t256;
+  } else {
+    // Cout <= 64: 128x64 tiles (a 128-wide tile would leave half its MFMA work on padding columns)
+    p.arm = Cout <= 64 ? 4 : 5;
+    p.buf = xbytes <= 0x7fffffffL && wbytes <= 0x7fffffffL;
+    const long tiles = (long)tiles128 * (p.arm == 4 ? 1 : (Cout + 127) / 128);
+    p.grid = (int)tiles;
+    const int nk = g.K / ig::BK;
+    const int s0 = (int)std::min<long>(4, (512 + tiles - 1) / tiles);
+    if (p.buf && tiles < 256 && s0 >= 2 && nk >= 2 * s0) {
+      p.kps = (nk + s0 - 1) / s0;
+      p.splits = (nk + p.kps - 1) / p.kps;   // every split non-empty
+    }
+  }
+  return p;
 }
-static int fwd_stat_tiles(const Geom& g, int M, int Cout) {
-  Fwd3Plan p;
-  if (fwd3_plan(g, Cout, p)) return p.ntile;
-  return (M + 127) / 128;
-}
+
+extern "C" int cmhar_conv3d_fwd_plan(const int* dims, int Cout) { return plan_fwd(make_geom(dims), Cout).arm; }
 extern "C" int cmhar_conv3d_fwd_tiles(const int* dims, int Cout) {
-  const Geom g = make_geom(dims);
-  if (!igemm_ok(g, Cout)) return -1;
-  return fwd_stat_tiles(g, g.N * g.To * g.Ho * g.Wo, Cout);
+  const FwdPlan p = plan_fwd(make_geom(dims), Cout);
+  return p.arm < 0 ? -1 : p.stat_tiles;
 }
 extern "C" long cmhar_conv3d_fwd_stats_floats(const int* dims, int Cout) {
   const int nt = cmhar_conv3d_fwd_tiles(dims, Cout);
-  if (nt <= 0) return -1;
-  const int ng = (nt + BN_TG - 1) / BN_TG;
-  return 2L * (nt + ng) * Cout + nt + ng;
-}
-
-// Split-K plan for the forward convs whose 128-row tile grid leaves most of the chip idle (R3D-18 layer 4: 3136 rows
-// × 512 outputs = 200 tiles for 512 workgroup slots): the (it, ih, channel-slice) K-steps split over nsplit workgroups
-// per tile, fp32 partials in the caller's workspace, conv_split_reduce sums them in order (+ residual) and rounds
-// once.  No BatchNorm tile statistics (the caller takes the statistics passes over z: small at these sizes).
-// 0 = not this plan.  CMHAR_FWD_SPLIT=0 turns it off (A/B runs).
-// The generic implicit GEMM (strided convs: R3D-18 layer 4's stride-2 3x3 conv, 3136 x 512 = 100 128x128 tiles, and
-// its 1x1 downsample) splits the same way over its BK-wide K-steps: split y takes kps of them (ig_split_kps).
-static int fwd_plan(const Geom& g, int Cout);
-static bool fwd_split_on() {
-  static const bool on = [] {
-    const char* v = getenv("CMHAR_FWD_SPLIT");
-    return !(v && v[0] == '0');
-  }();
-  return on;
-}
-static int ig_split_count(const Geom& g, int Cout, int& kps) {
-  kps = 0;
-  if (!fwd_split_on() || !igemm_ok(g, Cout)) return 0;
-  const int plan = fwd_plan(g, Cout);
-  if ((plan != 4 && plan != 5) || (long)g.N * g.T * g.H * g.W * g.C * 2 > 0x7fffffffL ||
-      (long)Cout * g.Kp * 2 > 0x7fffffffL)   // the buffer-resource instantiation only
-    return 0;
-  const int M = g.N * g.To * g.Ho * g.Wo;
-  const long tiles = (long)((M + 127) / 128) * (plan == 4 ? 1 : (Cout + 127) / 128);
-  if (tiles >= 256) return 0;
-  const int nk = g.K / ig::BK;
-  const int s0 = (int)std::min<long>(4, (512 + tiles - 1) / tiles);
-  if (s0 < 2 || nk < 2 * s0) return 0;
-  kps = (nk + s0 - 1) / s0;
-  return (nk + kps - 1) / kps;   // every split non-empty
-}
-static int fwd_split_count(const Geom& g, int Cout) {
-  if (!fwd_split_on() || !igemm_ok(g, Cout)) return 0;
-  int kps;
-  if (const int s = ig_split_count(g, Cout, kps)) return s;
-  Fwd3Plan p3;
-  if (fwd3_plan(g, Cout, p3)) return 0;
-  const int M = g.N * g.To * g.Ho * g.Wo;
-  const int Ls = (g.Wo - 1) * g.sw + g.kw;
-  if (g.kw != 3 || Cout % fr::TN || g.Wo > 255 || Ls > 255 || (long)g.N * g.T * g.H * g.W * g.C * 2 > (1L << 30) ||
-      (long)Cout * g.Kp * 2 > 0x7fffffffL)
-    return 0;
-  if ((long)((128 + g.Wo - 2) / g.Wo + 1) * Ls > fr::Cfg<128>::SQ) return 0;
-  const long t128 = (long)((M + 127) / 128) * (Cout / fr::TN);
-  if (t128 >= 256) return 0;
-  const int nks = g.kt * g.kh * (g.C / 64);
-  const int s = (int)std::min<long>(4, (512 + t128 - 1) / t128);
-  return s >= 2 && nks >= 2 * s ? s : 0;
+  return nt <= 0 ? -1 : tile_stats_layout(nt, Cout).floats;
 }
 extern "C" long cmhar_conv3d_fwd_split_ws(const int* dims, int Cout) {
-  const Geom g = make_geom(dims);
-  const int s = fwd_split_count(g, Cout);
-  return s ? (long)s * g.N * g.To * g.Ho * g.Wo * Cout : 0;
+  const FwdPlan p = plan_fwd(make_geom(dims), Cout);
+  return (long)p.splits * p.M * Cout;
 }
+
 extern "C" int cmhar_conv3d_fwd_split(const int* dims, int Cout, const void* x, const void* w, const void* res,
                                       void* z, float* ws, hipStream_t stream) {
   const Geom g = make_geom(dims);
-  const int s = fwd_split_count(g, Cout);
-  if (!s || !ws) return -1;
-  const int M = g.N * g.To * g.Ho * g.Wo;
-  int kps;
-  if (ig_split_count(g, Cout, kps)) {
-    if (fwd_plan(g, Cout) == 4)
-      conv3d_fwd_igemm<2, true><<<dim3((M + 127) / 128, s), 256, 0, stream>>>(
-          g, M, Cout, (const bf16*)x, (const bf16*)w, nullptr, nullptr, nullptr, kps, ws);
-    else
-      conv3d_fwd_igemm<4, true><<<dim3(((M + 127) / 128) * ((Cout + 127) / 128), s), 256, 0, stream>>>(
-          g, M, Cout, (const bf16*)x, (const bf16*)w, nullptr, nullptr, nullptr, kps, ws);
-    conv_split_reduce<<<grid_for((long)M * Cout / 8), 256, 0, stream>>>(M, Cout, s, ws, (const bf16*)res, (bf16*)z);
-    CMHAR_CHECK_LAUNCH();
-    return 0;
-  }
-  const int Ls = (g.Wo - 1) * g.sw + g.kw;
-  const int t128 = ((M + 127) / 128) * (Cout / fr::TN);
-  conv3d_fwd_rows<128><<<dim3(t128, s), 256, 0, stream>>>(g, M, Cout, Ls, (const bf16*)x, (const bf16*)w, nullptr,
-                                                         nullptr, nullptr, ws);
-  conv_split_reduce<<<grid_for((long)M * Cout / 8), 256, 0, stream>>>(M, Cout, s, ws, (const bf16*)res, (bf16*)z);
+  const FwdPlan p = plan_fwd(g, Cout);
+  if (!p.splits || !ws) return -1;
+  const dim3 grid(p.grid, p.splits);
+  if (p.arm == 2)
+    conv3d_fwd_rows<128><<<grid, 256, 0, stream>>>(g, p.M, Cout, p.Ls, (const bf16*)x, (const bf16*)w, nullptr, nullptr,
+                                                   nullptr, ws);
+  else if (p.arm == 4)
+    conv3d_fwd_igemm<2, true><<<grid, 256, 0, stream>>>(g, p.M, Cout, (const bf16*)x, (const bf16*)w, nullptr, nullptr,
+                                                        nullptr, p.kps, ws);
+  else
+    conv3d_fwd_igemm<4, true><<<grid, 256, 0, stream>>>(g, p.M, Cout, (const bf16*)x, (const bf16*)w, nullptr, nullptr,
+                                                        nullptr, p.kps, ws);
+  conv_split_reduce<<<grid_for((long)p.M * Cout / 8), 256, 0, stream>>>(p.M, Cout, p.splits, ws, (const bf16*)res,
+                                                                        (bf16*)z);
   CMHAR_CHECK_LAUNCH();
   return 0;
 }
 
-// Launch plan of cmhar_conv3d_fwd (exported as cmhar_conv3d_fwd_plan so tests pin the kernel a geometry takes):
-// 1 = nine-tap conv3d_fwd_rows3 (Cout = 64, 3x3 taps at unit H/W stride), 2 = row-slab conv3d_fwd_rows<128>,
-// 3 = row-slab conv3d_fwd_rows<256>, 4 = generic conv3d_fwd_igemm 128x64, 5 = generic conv3d_fwd_igemm 128x128;
-// -1 = not an implicit-GEMM geometry.  (The split-K plan is the caller's choice: cmhar_conv3d_fwd_split_ws > 0.)
-// CMHAR_FWD_ROWS=0: the generic gather kernel instead of the row-slab ones (A/B runs).
-static int fwd_plan(const Geom& g, int Cout) {
-  if (!igemm_ok(g, Cout)) return -1;
-  Fwd3Plan p3;
-  if (fwd3_plan(g, Cout, p3)) return 1;
-  static const bool rows_on = [] {
-    const char* v = getenv("CMHAR_FWD_ROWS");
-    return !(v && v[0] == '0');
-  }();
-  const int M = g.N * g.To * g.Ho * g.Wo;
-  const int Ls = (g.Wo - 1) * g.sw + g.kw;
-  auto fits = [&](int tm, int sq) { return (long)((tm + g.Wo - 2) / g.Wo + 1) * Ls <= sq; };   // rows a tile touches
-  if (rows_on && g.kw == 3 && Cout % fr::TN == 0 && g.Wo <= 255 && Ls <= 255 &&
-      (long)g.N * g.T * g.H * g.W * g.C * 2 <= (1L << 30) && (long)Cout * g.Kp * 2 <= 0x7fffffffL) {   // 32-bit offsets
-    // 256-row tiles while they give every CU a workgroup, else 128-row tiles (R3D-18 layer 4: 268 -> 164 us; layer 3
-    // at 392 256-row tiles measured 167 vs 199 us, so it keeps them)
-    const long t256 = (long)((M + 255) / 256) * (Cout / fr::TN);
-    const bool small = t256 < 256 && fits(128, fr::Cfg<128>::SQ);
-    if (small) return 2;
-    if (fits(256, fr::Cfg<256>::SQ)) return 3;
-  }
-  // Cout <= 64: 128x64 tiles (a 128-wide tile would leave half its MFMA work on padding columns)
-  return Cout <= 64 ? 4 : 5;
-}
-extern "C" int cmhar_conv3d_fwd_plan(const int* dims, int Cout) { return fwd_plan(make_geom(dims), Cout); }
-
 extern "C" int cmhar_conv3d_fwd(const int* dims, int Cout, const void* x, const void* w, const void* res, void* z,
                                 float* tile_stats, hipStream_t stream) {
   const Geom g = make_geom(dims);
-  const int plan = fwd_plan(g, Cout);
-  if (plan < 0) return -1;
-  const int M = g.N * g.To * g.Ho * g.Wo;
-  const int Ls = (g.Wo - 1) * g.sw + g.kw;
-  switch (plan) {
-    case 1: {
-      Fwd3Plan p3;
-      fwd3_plan(g, Cout, p3);
-      static const bool swz = [] {   // CMHAR_ROWS3_SWZ=0: the padded 144-B LDS rows (A/B runs)
-        const char* v = getenv("CMHAR_ROWS3_SWZ");
-        return !(v && v[0] == '0');
-      }();
-      if (swz)
-        conv3d_fwd_rows3<true><<<p3.ntile * (Cout / fr3::TN), 256, 0, stream>>>(
-            g, Cout, p3.R, p3.Ls, p3.cpf, (const bf16*)x, (const bf16*)w, (const bf16*)res, (bf16*)z, tile_stats);
-      else
-        conv3d_fwd_rows3<false><<<p3.ntile * (Cout / fr3::TN), 256, 0, stream>>>(
-            g, Cout, p3.R, p3.Ls, p3.cpf, (const bf16*)x, (const bf16*)w, (const bf16*)res, (bf16*)z, tile_stats);
+  const FwdPlan p = plan_fwd(g, Cout);
+  const int M = p.M;
+  switch (p.arm) {
+    case 1:
+      conv3d_fwd_rows3<<<p.grid, 256, 0, stream>>>(g, Cout, p.R, p.Ls, p.cpf, (const bf16*)x, (const bf16*)w,
+                                                   (const bf16*)res, (bf16*)z, tile_stats);
       break;
-    }
     case 2:
-      conv3d_fwd_rows<128><<<((M + 127) / 128) * (Cout / fr::TN), 256, 0, stream>>>(
-          g, M, Cout, Ls, (const bf16*)x, (const bf16*)w, (const bf16*)res, (bf16*)z, tile_stats);
+      conv3d_fwd_rows<128><<<p.grid, 256, 0, stream>>>(g, M, Cout, p.Ls, (const bf16*)x, (const bf16*)w,
+                                                       (const bf16*)res, (bf16*)z, tile_stats);
       break;
     case 3:
-      conv3d_fwd_rows<256><<<((M + 255) / 256) * (Cout / fr::TN), 256, 0, stream>>>(
-          g, M, Cout, Ls, (const bf16*)x, (const bf16*)w, (const bf16*)res, (bf16*)z, tile_stats);
+      conv3d_fwd_rows<256><<<p.grid, 256, 0, stream>>>(g, M, Cout, p.Ls, (const bf16*)x, (const bf16*)w,
+                                                       (const bf16*)res, (bf16*)z, tile_stats);
       break;
-    default: {
-      // 32-bit buffer offsets when x and the weights are under 2 GiB
-      const bool buf = (long)g.N * g.T * g.H * g.W * g.C * 2 <= 0x7fffffffL && (long)Cout * g.Kp * 2 <= 0x7fffffffL;
-#define IG(JN, BUF, GRID)                                                                                        \
-  conv3d_fwd_igemm<JN, BUF><<<GRID, 256, 0, stream>>>(g, M, Cout, (const bf16*)x, (const bf16*)w, (const bf16*)res, \
-                                                      (bf16*)z, tile_stats, g.K / ig::BK, nullptr)
-      if (plan == 4) {
-        if (buf) IG(2, true, (M + 127) / 128);
-        else IG(2, false, (M + 127) / 128);
+    case 4:
+    case 5: {
+#define IG(JN, BUF)                                                                                                 \
+  conv3d_fwd_igemm<JN, BUF><<<p.grid, 256, 0, stream>>>(g, M, Cout, (const bf16*)x, (const bf16*)w, (const bf16*)res, \
+                                                        (bf16*)z, tile_stats, g.K / ig::BK, nullptr)
+      if (p.arm == 4) {
+        if (p.buf) IG(2, true);
+        else IG(2, false);
       } else {
-        if (buf) IG(4, true, ((M + 127) / 128) * ((Cout + 127) / 128));
-        else IG(4, false, ((M + 127) / 128) * ((Cout + 127) / 128));
+        if (p.buf) IG(4, true);
+        else IG(4, false);
       }
 #undef IG
+      break;
     }
+    default: return -1;
   }
   CMHAR_CHECK_LAUNCH();
   return 0;
 }
 
 // ---- implicit stem entry points (bf16, C <= 4, kw <= 8, w-stride 2, Cout = 64) ----
-struct StemPlan { int R, cpf, ntile; };
+// Weight-gradient split target: at most 512 workgroups (rounded up, R3D-18's kt = 3 stem gave 513).  256 / 768 / 1024
+// workgroups measured 323.5 / 286.0 / 292.3 us per launch against 275.2 at 512 (A/B runs with CMHAR_STEM_WGS).
+constexpr int kStemWgradWgs = 512;
+struct StemPlan { int R, cpf, ntile, splits, tps; };   // splits x tps tiles: the weight gradient's blockIdx.y
 static bool stem_plan(const Geom& g, int Cout, StemPlan& p) {
   if (!geom_ok(g) || !(g.C <= 4 && g.kw <= 8 && g.sw == 2 && g.kh <= stm::KHMAX) || Cout != 64) return false;
   // staged positions: every window column a fragment reads, iw = 0..7 (weights zero past kw), all written (zeros)
@@ -2495,6 +1830,9 @@ static bool stem_plan(const Geom& g, int Cout, StemPlan& p) {
   if ((p.R - 1) * g.sh + g.kh > stm::UMAX) return false;
   p.cpf = (g.Ho + p.R - 1) / p.R;
   p.ntile = g.N * g.To * p.cpf;
+  const int s = max(1, min(kStemWgradWgs / g.kt, p.ntile / 8));
+  p.tps = (p.ntile + s - 1) / s;
+  p.splits = (p.ntile + p.tps - 1) / p.tps;
   return true;
 }
 extern "C" int cmhar_conv3d_stem_tiles(const int* dims, int Cout) {
@@ -2503,9 +1841,7 @@ extern "C" int cmhar_conv3d_stem_tiles(const int* dims, int Cout) {
 }
 extern "C" long cmhar_conv3d_stem_stats_floats(const int* dims, int Cout) {
   const int nt = cmhar_conv3d_stem_tiles(dims, Cout);
-  if (nt <= 0) return -1;
-  const int ng = (nt + BN_TG - 1) / BN_TG;
-  return 2L * (nt + ng) * Cout + nt + ng;
+  return nt <= 0 ? -1 : tile_stats_layout(nt, Cout).floats;
 }
 extern "C" int cmhar_conv_pack_stem(int Cout, int C, int kt, int kh, int kw, const float* w, void* out,
                                     hipStream_t stream) {
@@ -2524,223 +1860,151 @@ extern "C" int cmhar_conv3d_stem_fwd(const int* dims, int Cout, const void* x, c
   CMHAR_CHECK_LAUNCH();
   return 0;
 }
-static int stem_splits(const Geom& g, const StemPlan& p, int& tps) {
-  // at most 512 workgroups (rounded up, R3D-18's kt = 3 stem gave 513)
-  static const int wgs = [] {   // CMHAR_STEM_WGS: target workgroups (A/B runs)
-    const char* v = getenv("CMHAR_STEM_WGS");
-    return v ? max(1, atoi(v)) : 512;
-  }();
-  int s = max(1, min(wgs / g.kt, p.ntile / 8));
-  tps = (p.ntile + s - 1) / s;
-  return (p.ntile + tps - 1) / tps;
-}
 extern "C" long cmhar_conv3d_stem_wgrad_ws(const int* dims, int Cout) {
   const Geom g = make_geom(dims);
   StemPlan p;
   if (!stem_plan(g, Cout, p)) return -1;
-  int tps;
-  const int s = stem_splits(g, p, tps);
-  return (long)s * Cout * g.kt * g.kh * 32;
+  return (long)p.splits * Cout * g.kt * g.kh * 32;
 }
 extern "C" int cmhar_conv3d_stem_wgrad(const int* dims, int Cout, const void* x, const void* dz, float* dw4, float* ws,
                                        hipStream_t stream) {
   const Geom g = make_geom(dims);
   StemPlan p;
   if (!stem_plan(g, Cout, p) || !ws || !dw4) return -1;
-  int tps;
-  const int s = stem_splits(g, p, tps);
-  conv3d_stem_wgrad<<<dim3(g.kt, s), 64 * stm::KHMAX, 0, stream>>>(g, p.R, p.cpf, p.ntile, tps, (const bf16*)x,
-                                                                  (const bf16*)dz, ws);
+  conv3d_stem_wgrad<<<dim3(g.kt, p.splits), 64 * stm::KHMAX, 0, stream>>>(g, p.R, p.cpf, p.ntile, p.tps, (const bf16*)x,
+                                                                         (const bf16*)dz, ws);
   const long slab = (long)Cout * g.kt * g.kh * 32, n4 = slab / 4;
-  conv3d_wgrad_reduce<<<grid_for(n4), 256, 0, stream>>>(n4, s, slab, ws, dw4);
+  conv3d_wgrad_reduce<<<grid_for(n4), 256, 0, stream>>>(n4, p.splits, slab, ws, dw4);
   CMHAR_CHECK_LAUNCH();
   return 0;
 }
 
-// Split of the M contraction: ~2048 workgroups (8 per CU), slices of >= 512 rows (multiples of 64).  Measured on the
-// R3D-18 step (tools/bench_r3d.py, ms/step): 256 WGs 46.5, 512 44.3, 1024 41.1, 2048 39.8, 4096 39.8, 8192 40.7 —
-// short slices keep each XCD's gathered input window inside its L2.
-static int wgrad_splits(const Geom& g, int Cout, int& mlen) {
-  const int M = g.N * g.To * g.Ho * g.Wo;
-  const int tiles = ((Cout + 127) / 128) * ((g.K + 127) / 128);
-  static const int wgs = [] {   // CMHAR_WGRAD_IG_WGS: target workgroups (A/B runs)
-    const char* v = getenv("CMHAR_WGRAD_IG_WGS");
-    return v ? max(1, atoi(v)) : 2048;
-  }();
-  int s = max(1, wgs / tiles);   // whole rounds: rounding up can leave a last round of a few workgroups
-  const int smax = (M + 511) / 512;
-  if (s > smax) s = smax;
-  if (s < 1) s = 1;
-  mlen = ((M + s - 1) / s + 63) / 64 * 64;
-  return (M + mlen - 1) / mlen;
-}
+// ---- weight-gradient plan --------------------------------------------------------------------------------------
+// Workgroup targets of the split counts below; each was a CMHAR_*_WGS variable while it was measured.
+// Generic kernel (was CMHAR_WGRAD_IG_WGS), R3D-18 step (tools/bench_r3d.py, ms/step): 256 WGs 46.5, 512 44.3,
+// 1024 41.1, 2048 39.8, 4096 39.8, 8192 40.7 — short slices keep each XCD's gathered input window inside its L2.
+constexpr int kWgradIgWgs = 2048;
+// Row-slab kernel (was CMHAR_WGRAD_ROWS_WGS): ~2048 workgroups within the limits spelled out in plan_wgrad; 512 for
+// it and for the generic kernel measured within noise (step 2230 / 2232, 2226 / 2227 clips/s).
+constexpr int kWgradRowsWgs = 2048;
+// Nine-tap kernel (was CMHAR_WGRAD3_WGS): one 12-wave workgroup per CU, one full round (rounding the split count up
+// gave R3D-18 layer 1 513 workgroups: a third round of one; 512 = two rounds wrote twice the split partials — layer 1
+// 382.1 -> 358.6 us, layer 2 209.0 -> 199.5, layer 3 120.2 -> 110.4 at 256, step 2263 -> 2294 clips/s; 768 / 1024:
+// 2189 / 2188).
+constexpr int kWgrad3Wgs = 256;
 
-// Row-slab weight-gradient plan (conv3d_wgrad_rows): kw = 3, whole output rows of <= 64 positions per chunk, the
-// chunk's input slab within MAXQ rows, Cout a multiple of 64.  Splits of the output-row chunks give ~2048 workgroups
-// (>= 4 chunks each); every split writes a full [Cout][K] partial (the kernel covers all K columns of its tiles).
-struct RowsPlan { int R, Ls, rows, cps, splits, cot, grp, cpf, nchunk, cs; };
-// channels per workgroup of the nine-tap weight gradient (wr3::C3): CMHAR_WGRAD3_CS=32 / 64 overrides the default
-#ifndef CMHAR_WGRAD3_CS_DEFAULT
-#define CMHAR_WGRAD3_CS_DEFAULT 64
-#endif
-static int wgrad3_cs() {
-  static const int v = [] {
-    const char* e = getenv("CMHAR_WGRAD3_CS");
-    const int c = e ? atoi(e) : CMHAR_WGRAD3_CS_DEFAULT;
-    return c == 32 ? 32 : 64;
-  }();
-  return v;
-}
-static bool rows_plan(const Geom& g, int Cout, RowsPlan& p) {
-  static const bool on = [] {
-    const char* v = getenv("CMHAR_WGRAD_ROWS");
-    return !(v && v[0] == '0');
-  }();
-  if (!on || g.kw != 3 || g.Wo > wr::SLOTS || Cout % 64 || g.C % 64) return false;
-  // CMHAR_WGRAD_ROWS3=0: one-tap-row kernel for every shape; 1: nine-tap kernel for Cout = 64 only; 2 (default): also
-  // on 64-wide Cout slices of wider convs.  Measured slower there before the buffer-resource loads (R3D-18 layer 2
-  // 295.1 -> 311.0 us); with them faster (layer 2 278.7 -> 232.6 us, layer 3 143.3 -> 127.6, step 2198 -> 2221 clips/s,
-  // tools/gpu_r05_envab.sh): the nine-tap kernel's longer K per staged chunk beats the 128-wide tiles' slab reuse
-  static const int nine = [] {
-    const char* v = getenv("CMHAR_WGRAD_ROWS3");
-    return v && (v[0] == '0' || v[0] == '1') ? v[0] - '0' : 2;
-  }();
-  if (nine && (nine == 2 || Cout == 64) && g.kh == 3 && g.sh == 1 && g.sw == 1) {
-    // chunks of R output rows of one frame, balanced over the frame (as the nine-tap forward's tiles)
+// Launch plan of cmhar_conv3d_wgrad (arm exported as cmhar_conv3d_wgrad_plan for tests): 1 = nine-tap
+// conv3d_wgrad_rows3, 2 = row-slab conv3d_wgrad_rows with 128-wide Cout tiles, 3 = the same with 64-wide tiles,
+// 4 = generic conv3d_wgrad_igemm; -1 = not implicit-GEMM.  The grid is tiles x splits; with splits > 1 every split
+// writes a full [Cout][K] fp32 partial to the workspace (cmhar_conv3d_wgrad_ws) and conv3d_wgrad_reduce sums them.
+//
+// Row-slab arms (conv3d_wgrad_rows): kw = 3, whole output rows of <= 64 positions per chunk, the chunk's input slab
+// within MAXQ rows, Cout and C multiples of 64, x and dz within 1 GiB (32-bit buffer offsets).  The nine-tap kernel
+// takes the 3x3 stride-1 geometries among them, also on 64-wide Cout slices of wider convs.  That measured slower
+// before the buffer-resource loads (R3D-18 layer 2 295.1 -> 311.0 us) and faster with them (layer 2 278.7 -> 232.6 us,
+// layer 3 143.3 -> 127.6, step 2198 -> 2221 clips/s, tools/gpu_r05_envab.sh, CMHAR_WGRAD_ROWS3=1 against 2): the
+// nine-tap kernel's longer K per staged chunk beats the 128-wide tiles' slab reuse.
+struct WgradPlan {
+  int arm = -1;
+  int M = 0, tiles = 0, splits = 1;
+  int R = 0, Ls = 0, rows = 0, cps = 0;   // arms 1-3: rows per chunk, slab row length, output rows, chunks per split
+  int cpf = 0, nchunk = 0;                // arm 1: chunks per frame, chunks
+  int mlen = 0;                           // arm 4: output rows per split
+};
+static WgradPlan plan_wgrad(const Geom& g, int Cout) {
+  WgradPlan p;
+  if (!igemm_ok(g, Cout)) return p;
+  p.M = g.N * g.To * g.Ho * g.Wo;
+  p.rows = g.N * g.To * g.Ho;
+  p.Ls = (g.Wo - 1) * g.sw + g.kw;
+  const long partial = (long)Cout * g.K * 4;   // bytes of one split's dW partial
+  const bool slab = g.kw == 3 && g.Wo <= wr::SLOTS && Cout % 64 == 0 && g.C % 64 == 0 &&
+                    (long)g.N * g.T * g.H * g.W * g.C * 2 <= (1L << 30) && (long)p.M * Cout * 2 <= (1L << 30);
+  if (slab && g.kh == 3 && g.sh == 1 && g.sw == 1) {
+    // chunks of R output rows of one frame, balanced over the frame (as the nine-tap forward's tiles), and >= 3/4 of
+    // the 256 slots used: layer 4's 7 x 7 frames keep the one-tap-row kernel
     const int r0 = min(wr3::SLOTS / g.Wo, g.Ho);
     const int cpf = (g.Ho + r0 - 1) / r0, R = (g.Ho + cpf - 1) / cpf;
-    const int Ls3 = g.Wo - 1 + g.kw;
-    // (and >= 3/4 of the 256 slots used: layer 4's 7 x 7 frames keep the one-tap-row kernel); x and dz within 1 GiB
-    // (32-bit buffer offsets)
-    if ((R + 2) * Ls3 <= wr3::SQ && (cpf - 1) * R < g.Ho && 4 * R * g.Wo >= 3 * wr3::SLOTS &&
-        (long)g.N * g.T * g.H * g.W * g.C * 2 <= (1L << 30) && (long)g.N * g.To * g.Ho * g.Wo * Cout * 2 <= (1L << 30)) {
-      p.grp = 9;
-      p.cot = 64;
-      p.cs = wgrad3_cs();
+    if ((R + 2) * p.Ls <= wr3::SQ && (cpf - 1) * R < g.Ho && 4 * R * g.Wo >= 3 * wr3::SLOTS) {
+      p.arm = 1;
       p.R = R;
-      p.Ls = Ls3;
       p.cpf = cpf;
-      p.nchunk = g.N * g.To * p.cpf;
-      const int tiles = g.kt * (g.C / p.cs) * (Cout / 64);
-      // one 12-wave workgroup per CU (CS = 32: two 6-wave ones): one full round (rounding the split count up gave R3D-18 layer 1 513
-      // workgroups: a third round of one; 512 = two rounds wrote twice the split partials — layer 1 382.1 -> 358.6 us,
-      // layer 2 209.0 -> 199.5, layer 3 120.2 -> 110.4 at 256, step 2263 -> 2294 clips/s; 768 / 1024: 2189 / 2188),
-      // >= 4 chunks each, <= ~80 MB of split partials
-      static const int wgs = [] {   // CMHAR_WGRAD3_WGS: target workgroups (A/B runs)
-        const char* v = getenv("CMHAR_WGRAD3_WGS");
-        return v ? max(1, atoi(v)) : 256;
-      }();
-      int s = max(1, (p.cs == 64 ? wgs : 2 * wgs) / tiles);
-      s = min(s, (int)((80L << 20) / ((long)Cout * g.K * 4)));
+      p.nchunk = g.N * g.To * cpf;
+      p.tiles = g.kt * (g.C / wr3::CS) * (Cout / 64);
+      // >= 4 chunks per split, <= ~80 MB of split partials
+      int s = max(1, kWgrad3Wgs / p.tiles);
+      s = min(s, (int)((80L << 20) / partial));
       s = max(1, min(s, p.nchunk / 4));
       p.cps = (p.nchunk + s - 1) / s;
       p.splits = (p.nchunk + p.cps - 1) / p.cps;
-      p.rows = g.N * g.To * g.Ho;
-      return true;
+      return p;
     }
   }
-  p.cs = 64;
-  p.R = wr::SLOTS / g.Wo;
-  p.Ls = (g.Wo - 1) * g.sw + g.kw;
-  if (p.R * p.Ls > wr::MAXQ) return false;
-  // 32-bit buffer offsets of x and dz
-  if ((long)g.N * g.T * g.H * g.W * g.C * 2 > (1L << 30) || (long)g.N * g.To * g.Ho * g.Wo * Cout * 2 > (1L << 30))
-    return false;
-  p.rows = g.N * g.To * g.Ho;
-  p.cot = Cout % 128 == 0 ? 128 : 64;
-  // Cout = 64: three kh taps per workgroup when their slabs fit 64 rows each
-  // one kh tap per workgroup: three (the whole kh column, 576 dW columns per staged dz chunk) measured 4 % slower on
-  // the R3D-18 step — one workgroup per CU at 213 VGPRs, and a third of the workgroups to hide the gather latency
-  p.grp = 1;
-  const int nchunk = (p.rows + p.R - 1) / p.R;
-  const int tiles = g.kt * (g.kh / p.grp) * (g.C / 64) * (Cout / p.cot);
-  // at most ~2048 workgroups, >= 8 chunks each, and at most ~56 MB of fp32 partials (every split adds a Cout x K
-  // slab that is written here and read back by the reduce: at 2048 workgroups that was ~200 MB per conv, 1.7 ms per
-  // step); within that, the split count with the least time ∝ rounds of the 512 workgroup slots x chunks per split
-  // (whole rounds: R3D-18 layer 3 takes 7 splits = 504 workgroups, not 6 = 432)
-  static const int wgs = [] {   // CMHAR_WGRAD_ROWS_WGS: target workgroups (A/B runs)
-    const char* v = getenv("CMHAR_WGRAD_ROWS_WGS");
-    return v ? max(1, atoi(v)) : 2048;
-  }();
-  const int smax = max(1, min(min(wgs / tiles, (int)((56L << 20) / ((long)Cout * g.K * 4))), nchunk / 8));
-  long best = -1;
-  for (int c = 1; c <= smax; ++c) {
-    const int cps = (nchunk + c - 1) / c, sp = (nchunk + cps - 1) / cps;
-    const long t = (long)((tiles * sp + 511) / 512) * cps;
-    if (best < 0 || t < best) { best = t; p.cps = cps; p.splits = sp; }
+  if (slab && (wr::SLOTS / g.Wo) * p.Ls <= wr::MAXQ) {
+    p.R = wr::SLOTS / g.Wo;
+    // one kh tap per workgroup: three (the whole kh column, 576 dW columns per staged dz chunk) measured 4 % slower on
+    // the R3D-18 step — one workgroup per CU at 213 VGPRs, and a third of the workgroups to hide the gather latency
+    const int cot = Cout % 128 == 0 ? 128 : 64;
+    p.arm = cot == 128 ? 2 : 3;
+    const int nchunk = (p.rows + p.R - 1) / p.R;
+    p.tiles = g.kt * g.kh * (g.C / 64) * (Cout / cot);
+    // at most ~2048 workgroups, >= 8 chunks each, and at most ~56 MB of fp32 partials (every split adds a Cout x K
+    // slab that is written here and read back by the reduce: at 2048 workgroups that was ~200 MB per conv, 1.7 ms per
+    // step); within that, the split count with the least time ∝ rounds of the 512 workgroup slots x chunks per split
+    // (whole rounds: R3D-18 layer 3 takes 7 splits = 504 workgroups, not 6 = 432)
+    const int smax = max(1, min(min(kWgradRowsWgs / p.tiles, (int)((56L << 20) / partial)), nchunk / 8));
+    long best = -1;
+    for (int c = 1; c <= smax; ++c) {
+      const int cps = (nchunk + c - 1) / c, sp = (nchunk + cps - 1) / cps;
+      const long t = (long)((p.tiles * sp + 511) / 512) * cps;
+      if (best < 0 || t < best) { best = t; p.cps = cps; p.splits = sp; }
+    }
+    return p;
   }
-  return true;
+  // Generic kernel, split over the M contraction: ~2048 workgroups (8 per CU) in whole rounds (rounding up can leave a
+  // last round of a few workgroups), slices of >= 512 rows (multiples of 64)
+  p.arm = 4;
+  p.tiles = ((Cout + 127) / 128) * ((g.K + 127) / 128);
+  const int s = max(1, min(kWgradIgWgs / p.tiles, (p.M + 511) / 512));
+  p.mlen = ((p.M + s - 1) / s + 63) / 64 * 64;
+  p.splits = (p.M + p.mlen - 1) / p.mlen;
+  return p;
 }
 
-// Launch plan of cmhar_conv3d_wgrad (exported for tests): 1 = nine-tap conv3d_wgrad_rows3, 2 = row-slab
-// conv3d_wgrad_rows with 128-wide Cout tiles, 3 = the same with 64-wide tiles, 4 = generic conv3d_wgrad_igemm; each
-// followed by conv3d_wgrad_reduce when cmhar_conv3d_wgrad_ws > 0 (split partials); -1 = not implicit-GEMM.
-extern "C" int cmhar_conv3d_wgrad_plan(const int* dims, int Cout) {
-  const Geom g = make_geom(dims);
-  if (!igemm_ok(g, Cout)) return -1;
-  RowsPlan rp;
-  if (rows_plan(g, Cout, rp)) return rp.grp == 9 ? 1 : rp.cot == 128 ? 2 : 3;
-  return 4;
-}
+extern "C" int cmhar_conv3d_wgrad_plan(const int* dims, int Cout) { return plan_wgrad(make_geom(dims), Cout).arm; }
 
 extern "C" long cmhar_conv3d_wgrad_ws(const int* dims, int Cout) {
   const Geom g = make_geom(dims);
-  if (!igemm_ok(g, Cout)) return -1;
-  RowsPlan rp;
-  if (rows_plan(g, Cout, rp)) return rp.splits > 1 ? (long)rp.splits * Cout * g.K : 0;
-  int mlen;
-  const int s = wgrad_splits(g, Cout, mlen);
-  return s > 1 ? (long)s * Cout * g.K : 0;
+  const WgradPlan p = plan_wgrad(g, Cout);
+  if (p.arm < 0) return -1;
+  return p.splits > 1 ? (long)p.splits * Cout * g.K : 0;
 }
 
 extern "C" int cmhar_conv3d_wgrad(const int* dims, int Cout, const void* x, const void* dz, float* dw, float* ws,
                                   hipStream_t stream) {
   const Geom g = make_geom(dims);
-  if (!igemm_ok(g, Cout)) return -1;
-  const int M = g.N * g.To * g.Ho * g.Wo;
-  RowsPlan rp;
-  if (rows_plan(g, Cout, rp)) {
-    if (rp.splits > 1 && !ws) return -2;
-    float* dst = rp.splits > 1 ? ws : dw;
-    if (rp.grp == 9) {
-      const dim3 grid3(g.kt * (g.C / rp.cs) * (Cout / 64), rp.splits);
-      if (rp.cs == 32)
-        conv3d_wgrad_rows3<32><<<grid3, wr3::C3<32>::NT, 0, stream>>>(g, Cout, rp.R, rp.Ls, rp.cpf, rp.nchunk, rp.cps,
-                                                                      (const bf16*)x, (const bf16*)dz, dst);
-      else
-        conv3d_wgrad_rows3<64><<<grid3, wr3::C3<64>::NT, 0, stream>>>(g, Cout, rp.R, rp.Ls, rp.cpf, rp.nchunk, rp.cps,
-                                                                      (const bf16*)x, (const bf16*)dz, dst);
-      if (rp.splits > 1) {
-        const long slab = (long)Cout * g.K, n4 = slab / 4;
-        conv3d_wgrad_reduce<<<grid_for(n4), 256, 0, stream>>>(n4, rp.splits, slab, ws, dw);
-      }
-      CMHAR_CHECK_LAUNCH();
-      return 0;
-    }
-    const int tiles = g.kt * (g.kh / rp.grp) * (g.C / 64) * (Cout / rp.cot);
-    const dim3 grid(tiles, rp.splits);
-#define WR(COT, G, SQ, NW)                                                                                       \
-  conv3d_wgrad_rows<COT, G, SQ, NW><<<grid, 64 * NW, 0, stream>>>(g, Cout, rp.R, rp.Ls, rp.rows, rp.cps,          \
-                                                                  (const bf16*)x, (const bf16*)dz, dst)
-    if (rp.cot == 128) WR(128, 1, 136, 4);
-    else WR(64, 1, 136, 4);
-#undef WR
-    if (rp.splits > 1) {
-      const long slab = (long)Cout * g.K, n4 = slab / 4;
-      conv3d_wgrad_reduce<<<grid_for(n4), 256, 0, stream>>>(n4, rp.splits, slab, ws, dw);
-    }
-    CMHAR_CHECK_LAUNCH();
-    return 0;
+  const WgradPlan p = plan_wgrad(g, Cout);
+  if (p.arm < 0) return -1;
+  if (p.splits > 1 && !ws) return -2;
+  float* dst = p.splits > 1 ? ws : dw;
+  const dim3 grid(p.tiles, p.splits);
+  const bf16 *xb = (const bf16*)x, *dzb = (const bf16*)dz;
+  switch (p.arm) {
+    case 1:
+      conv3d_wgrad_rows3<<<grid, wr3::NT, 0, stream>>>(g, Cout, p.R, p.Ls, p.cpf, p.nchunk, p.cps, xb, dzb, dst);
+      break;
+    case 2:
+      conv3d_wgrad_rows<128, 1, 136, 4><<<grid, 256, 0, stream>>>(g, Cout, p.R, p.Ls, p.rows, p.cps, xb, dzb, dst);
+      break;
+    case 3:
+      conv3d_wgrad_rows<64, 1, 136, 4><<<grid, 256, 0, stream>>>(g, Cout, p.R, p.Ls, p.rows, p.cps, xb, dzb, dst);
+      break;
+    default:
+      conv3d_wgrad_igemm<<<grid, 256, 0, stream>>>(g, p.M, Cout, p.mlen, xb, dzb, dst);
   }
-  int mlen;
-  const int s = wgrad_splits(g, Cout, mlen);
-  if (s > 1 && !ws) return -2;
-  const int tiles = ((Cout + 127) / 128) * ((g.K + 127) / 128);
-  dim3 grid(tiles, s);
-  conv3d_wgrad_igemm<<<grid, 256, 0, stream>>>(g, M, Cout, mlen, (const bf16*)x, (const bf16*)dz, s > 1 ? ws : dw);
-  if (s > 1) {
+  if (p.splits > 1) {
     const long slab = (long)Cout * g.K, n4 = slab / 4;
-    conv3d_wgrad_reduce<<<grid_for(n4), 256, 0, stream>>>(n4, s, slab, ws, dw);
+    conv3d_wgrad_reduce<<<grid_for(n4), 256, 0, stream>>>(n4, p.splits, slab, ws, dw);
   }
   CMHAR_CHECK_LAUNCH();
   return 0;

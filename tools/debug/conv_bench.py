@@ -1,6 +1,6 @@
 """Per-layer timing of the R3D-18 implicit-GEMM conv kernels at the bench geometry (B clips of 16x112^2, NDHWC bf16):
-forward (cmhar_conv3d_fwd: row-slab or generic kernel per the library's plan / CMHAR_FWD_ROWS) and weight gradient
-(cmhar_conv3d_wgrad; CMHAR_WGRAD_ROWS), each layer's algorithmic TFLOP/s.
+forward (cmhar_conv3d_fwd: row-slab or generic kernel per the library's plan) and weight gradient
+(cmhar_conv3d_wgrad), each layer's algorithmic TFLOP/s.
     python tools/debug/conv_bench.py [--batch 32] [--reps 10]"""
 import argparse
 import ctypes
