@@ -76,6 +76,8 @@ _SIGS = {
     'cmhar_siglip_ws': (i64, [i32, i32]),
     'cmhar_siglip_loss': (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]),
     'cmhar_tubelet_im2col': (i32, [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    'cmhar_tubelet_im2col_gather': (i32, [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
+    'cmhar_gather_rows_f32': (i32, [i32, i32, vp, i64, i32, vp, vp, i64, vp]),
     'cmhar_imu_embed_fwd': (i32, [i32, i32, i32, i32, i32, i32, i32, i32, vp, C.POINTER(vp), C.POINTER(vp), vp, vp,
                                   vp, vp]),
     'cmhar_imu_embed_bwd': (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(vp),

@@ -101,6 +101,10 @@ class ModelConfig:
     videomae_qkv_bias: bool = True
     videomae_num_frames: Optional[int] = None
     videomae_image_size: Optional[int] = None
+    # Masked-token pretraining (FLIP on VideoMAE's tube masks; not in the reference, read with getattr defaults): in
+    # training mode the VideoMAE backbone encodes a random 1 - video_mask_ratio of the video tokens; eval encodes all.
+    video_mask_ratio: float = 0.0        # in [0, 1); 0 = off
+    video_mask_mode: str = 'tube'        # 'tube' (one spatial keep-set per clip at every time step) or 'random'
 
 
 @dataclass

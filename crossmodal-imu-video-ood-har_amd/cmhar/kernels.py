@@ -597,6 +597,45 @@ def tubelet_im2col(video, tub, P, out_dtype):
     return out
 
 
+def tubelet_im2col_gather(video, tub, P, out_dtype, keep_idx):
+    """Rows b·Lt + keep_idx[b][j] of tubelet_im2col(video, ...) as a [B·Lkeep, C·tub·P·P] matrix, bit for bit, without
+    reading the patches that are not kept.  keep_idx: contiguous int32 device [B, Lkeep] with values in [0, Lt) (the
+    kernel clamps them; it does not report a bad one)."""
+    if video.dtype != torch.float32 or video.dim() != 5 or not video.is_contiguous() or not video.is_cuda:
+        raise ValueError('video must be a contiguous fp32 (B,T,C,H,W) device tensor')
+    B, T, Cc, H, W = video.shape
+    if B < 1 or T % tub or H % P or W % P or P % 8 or video.data_ptr() % 16:
+        raise ValueError(f'video {tuple(video.shape)} incompatible with tubelet {tub} patch {P}')
+    if (not isinstance(keep_idx, torch.Tensor) or keep_idx.dtype != torch.int32 or keep_idx.dim() != 2 or
+            keep_idx.shape[0] != B or keep_idx.shape[1] < 1 or not keep_idx.is_contiguous()):
+        raise ValueError(f'keep_idx must be a contiguous int32 [{B}, Lkeep >= 1] tensor')
+    if keep_idx.device != video.device:
+        raise ValueError('keep_idx must be a device tensor on the video\'s device')
+    if out_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(f'unsupported patch dtype {out_dtype}')
+    Lkeep = keep_idx.shape[1]
+    out = torch.empty(B * Lkeep, Cc * tub * P * P, dtype=out_dtype, device=video.device)
+    call('cmhar_tubelet_im2col_gather', L.dtype_code(out_dtype), B, T, Cc, H, W, tub, P, ptr(video), ptr(keep_idx),
+         Lkeep, ptr(out), L.stream(video.device))
+    return out
+
+
+def gather_rows(table, idx):
+    """out[m] = table[idx[m]] for an fp32 device matrix `table` [R, N] and int32 device indices (any shape, flattened;
+    clamped into [0, R) by the kernel).  Returns a contiguous fp32 [idx.numel(), N] matrix."""
+    _check_2d(table, 'table')
+    if table.dtype != torch.float32 or table.shape[0] < 1 or table.shape[1] < 1:
+        raise ValueError('table must be a non-empty fp32 matrix')
+    if (not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32 or not idx.is_contiguous() or
+            idx.numel() < 1 or idx.device != table.device):
+        raise ValueError('idx must be a non-empty contiguous int32 tensor on the table\'s device')
+    M, N = idx.numel(), table.shape[1]
+    out = torch.empty(M, N, dtype=torch.float32, device=table.device)
+    call('cmhar_gather_rows_f32', M, N, ptr(table), table.stride(0), table.shape[0], ptr(idx), ptr(out),
+         out.stride(0), L.stream(table.device))
+    return out
+
+
 def ptr_array(tensors):
     arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
     return arr

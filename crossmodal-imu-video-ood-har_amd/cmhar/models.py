@@ -24,7 +24,8 @@ from .imu import IMUEncoder, PatchEmbedding
 from .cnn2d import MobileNetV2Features, ResNet18Features, run_cnn2d
 from .fusion import _TokenMeanFn
 from .r3d import R3D18, run_r3d
-from .videomae import VideoMAEBackbone, default_videomae_config, run_backbone
+from .videomae import (VideoMAEBackbone, default_videomae_config, mask_to_keep_indices, run_backbone,
+                       tube_keep_indices)
 
 __all__ = ['PatchEmbedding', 'IMUEncoder', 'VideoEncoder', 'ProjectionHead', 'CrossModalModel', 'IMUClassifier']
 
@@ -119,11 +120,37 @@ class VideoEncoder(nn.Module):
         self.projection = nn.Linear(self.feature_dim, model_cfg.video_d_model)
         if vb in ('resnet18', 'mobilenet_v2'):
             self.temporal_pool = nn.AdaptiveAvgPool1d(1)            # models.py:182-183 (no parameters)
+        # masked-token pretraining (not in the reference: getattr defaults)
+        self.video_mask_ratio = float(getattr(model_cfg, 'video_mask_ratio', 0.0))
+        self.video_mask_mode = getattr(model_cfg, 'video_mask_mode', 'tube')
+        if not 0.0 <= self.video_mask_ratio < 1.0:
+            raise ValueError(f'video_mask_ratio must lie in [0, 1), got {self.video_mask_ratio}')
+        if self.video_mask_mode not in ('tube', 'random'):
+            raise ValueError(f"video_mask_mode must be 'tube' or 'random', got {self.video_mask_mode!r}")
+        if self.video_mask_ratio > 0.0 and not self.is_videomae:
+            raise ValueError(f'video_mask_ratio = {self.video_mask_ratio} needs the VideoMAE backbone: {vb!r} has no '
+                             f'token masking')
 
-    def forward(self, x):
-        """x (B, T, C, H, W) → (B, video_d_model)."""
+    def _keep_indices(self, x, bool_masked_pos):
+        """Kept-token list of this call, or None to encode every token: an explicit HF-style mask in any mode, else
+        random tube / token masks in training mode when video_mask_ratio > 0 (eval encodes all tokens, as FLIP
+        evaluates).  Token 0 is always kept by the random masks, so the readout stays the same patch token."""
+        cfg = self.backbone.config
+        Tp, Hp = x.shape[1] // cfg.tubelet_size, cfg.image_size // cfg.patch_size
+        if bool_masked_pos is not None:
+            return mask_to_keep_indices(bool_masked_pos, x.shape[0], Tp * Hp * Hp).to(x.device)
+        if not self.training or self.video_mask_ratio <= 0.0:
+            return None
+        return tube_keep_indices(x.shape[0], Tp, Hp, Hp, self.video_mask_ratio, device=x.device,
+                                 mode=self.video_mask_mode, keep_first=True,
+                                 multiple=8 if self.backbone.compute_dtype == 'bf16' else 1)
+
+    def forward(self, x, bool_masked_pos=None):
+        """x (B, T, C, H, W) → (B, video_d_model).  bool_masked_pos (VideoMAE only): bool [B, Lt], True = dropped."""
         if x.dim() != 5:
             raise ValueError(f'expected (B, T, C, H, W) video, got {tuple(x.shape)}')
+        if bool_masked_pos is not None and not self.is_videomae:
+            raise ValueError('bool_masked_pos needs the VideoMAE backbone')
         if isinstance(self.backbone, (ResNet18Features, MobileNetV2Features)):
             # models.py:208-216: per-frame CNN + 2-D average pool → per-frame projection → mean over the T frames
             B, T = x.shape[:2]
@@ -131,7 +158,8 @@ class VideoEncoder(nn.Module):
             return _TokenMeanFn.apply(feats, B, T)
         if not self.is_videomae:                                  # r3d_18: pooled 3-D CNN features
             return linear_fp32(run_r3d(self.backbone, x, self.training), self.projection)
-        feat = run_backbone(self.backbone, x, token0_only=True)   # last_hidden_state[:, 0]  (models.py:201)
+        # last_hidden_state[:, 0]  (models.py:201)
+        feat = run_backbone(self.backbone, x, token0_only=True, keep_idx=self._keep_indices(x, bool_masked_pos))
         return linear_fp32(feat, self.projection)                 # models.py:202
 
 

@@ -17,6 +17,10 @@ output, MLP and LayerNorm 2 on the token-0 rows only (_last_layer_token0_fwd / _
 none of the rows the reference computes and drops.  Compute dtype: bf16 (MFMA, fp32 accumulate),
 fp32 (exact parity mode), or fp16 (MFMA, fp32 accumulate; forward only — the inference path of BASELINE config 5);
 master weights and their gradients stay fp32.
+
+Masked-token encoding (`bool_masked_pos` / `keep_idx`, FLIP-style pretraining): the patch matrix and the position rows
+are gathered for the kept tokens only (csrc/token_mask.hip) and the same launch sequence runs at Lkeep tokens per clip;
+`tube_keep_indices` draws VideoMAE's tube masks on the device.
 """
 from __future__ import annotations
 
@@ -193,10 +197,78 @@ class VideoMAEBackbone(L.NoReplicate, nn.Module):
         return self._packs
 
     def forward(self, pixel_values, bool_masked_pos=None, **kwargs):
+        """`VideoMAEModel.forward` (modeling_videomae.py:109-122).  bool_masked_pos: bool [B, Lt], True = the token is
+        dropped after the position add; the kept tokens stay in ascending order and every clip must keep the same
+        number (`embeddings[~mask].reshape(B, -1, C)`).  Returns last_hidden_state [B, Lkeep, Hd].  Only the kept
+        patches are read and encoded.  Converting the mask costs ONE host synchronisation (the kept count sizes every
+        launch); `run_backbone(..., keep_idx=tube_keep_indices(...))` has none."""
+        keep_idx = None
         if bool_masked_pos is not None:
-            raise NotImplementedError('masked-token pretraining is not on the accelerated path')
-        out = run_backbone(self, pixel_values, token0_only=False)
+            if pixel_values.dim() != 5:
+                raise ValueError(f'expected (B, T, C, H, W) pixel_values, got {tuple(pixel_values.shape)}')
+            cfg = self.config
+            Lt = (cfg.num_frames // cfg.tubelet_size) * (cfg.image_size // cfg.patch_size) ** 2
+            keep_idx = mask_to_keep_indices(bool_masked_pos, pixel_values.shape[0], Lt).to(pixel_values.device)
+        out = run_backbone(self, pixel_values, token0_only=False, keep_idx=keep_idx)
         return VideoMAEOutput(out)
+
+
+def mask_to_keep_indices(bool_masked_pos, B: int, Lt: int) -> torch.Tensor:
+    """HF `bool_masked_pos` (bool [B, Lt], True = dropped) → int32 [B, Lkeep] kept token numbers, ascending per clip,
+    on the mask's device.  One host synchronisation (the per-clip kept counts).  ValueError for a wrong shape or
+    dtype, clips that keep different numbers of tokens, or clips that keep none."""
+    if not isinstance(bool_masked_pos, torch.Tensor) or bool_masked_pos.dtype != torch.bool:
+        raise ValueError(f'bool_masked_pos must be a torch.bool tensor, got '
+                         f'{getattr(bool_masked_pos, "dtype", type(bool_masked_pos))}')
+    if tuple(bool_masked_pos.shape) != (B, Lt):
+        raise ValueError(f'bool_masked_pos must have shape [{B}, {Lt}] (batch, tokens), got '
+                         f'{tuple(bool_masked_pos.shape)}')
+    kept = (~bool_masked_pos).sum(dim=1)
+    lo, hi = (int(v) for v in torch.stack(torch.aminmax(kept)).tolist())       # the one host sync
+    if lo != hi:
+        raise ValueError(f'every clip must keep the same number of tokens; bool_masked_pos keeps between {lo} and '
+                         f'{hi}')
+    if lo < 1:
+        raise ValueError('bool_masked_pos masks every token: at least one token per clip must be kept')
+    # stable sort of the mask: the kept (False) tokens first, in ascending token order
+    order = torch.sort(bool_masked_pos.to(torch.uint8), dim=1, stable=True).indices
+    return order[:, :lo].to(torch.int32).contiguous()
+
+
+def tube_keep_indices(B: int, Tp: int, Hp: int, Wp: int, mask_ratio: float, *, device, mode: str = 'tube',
+                      keep_first: bool = True, multiple: int = 1, generator=None) -> torch.Tensor:
+    """Random kept-token lists for masked-token pretraining (FLIP on VideoMAE's tube masks): int32 [B, Lkeep] token
+    numbers in the (t', h', w') order of the patch matrix, ascending per clip, drawn on `device` (CPU too) without a
+    host synchronisation.
+
+    mode 'tube': one set of spatial patches per clip, kept at all Tp time steps (VideoMAE's tube masking);
+    mode 'random': tokens drawn independently over all Tp·Hp·Wp.  With n the number of units drawn from (Hp·Wp
+    spatial patches / all tokens), the kept count is max(1, round((1 − mask_ratio)·n)), raised to the next count for
+    which Lkeep % multiple == 0 (the bf16 weight-gradient GEMMs contract over the token rows in multiples of 8).
+    keep_first: spatial patch 0 (hence token 0) is always kept, so that `last_hidden_state[:, 0]` is the same patch
+    token as in the unmasked model.  Randomness: torch.rand on `device`, from the global RNG or `generator`."""
+    if min(B, Tp, Hp, Wp) < 1:
+        raise ValueError(f'B, Tp, Hp, Wp must be positive, got {(B, Tp, Hp, Wp)}')
+    if not 0.0 <= mask_ratio < 1.0:
+        raise ValueError(f'mask_ratio must lie in [0, 1), got {mask_ratio}')
+    if mode not in ('tube', 'random'):
+        raise ValueError(f"mode must be 'tube' or 'random', got {mode!r}")
+    if multiple < 1:
+        raise ValueError(f'multiple must be >= 1, got {multiple}')
+    n, rep = (Hp * Wp, Tp) if mode == 'tube' else (Tp * Hp * Wp, 1)
+    k = max(1, round((1.0 - mask_ratio) * n))
+    while k <= n and (k * rep) % multiple:
+        k += 1
+    if k > n:
+        raise ValueError(f'no kept count in [{max(1, round((1.0 - mask_ratio) * n))}, {n}] makes the {mode} mask keep '
+                         f'a multiple of {multiple} tokens (Tp {Tp}, Hp {Hp}, Wp {Wp})')
+    noise = torch.rand(B, n, device=device, generator=generator)
+    if keep_first:
+        noise[:, 0] = -1.0
+    ids = torch.argsort(noise, dim=1)[:, :k].sort(dim=1).values
+    if rep > 1:
+        ids = (torch.arange(rep, device=ids.device).view(1, rep, 1) * n + ids.view(B, 1, k)).reshape(B, rep * k)
+    return ids.to(torch.int32).contiguous()
 
 
 # Input-gradient GEMMs dX = dY·W on the transposed bf16 weight copy Wᵀ [K, N] in the FORWARD layout (K-contiguous B
@@ -281,7 +353,19 @@ def m_inter(layer):
     return layer.intermediate.dense.weight.shape[0]
 
 
-def _forward_impl(m: VideoMAEBackbone, video: torch.Tensor, save: bool, token0_only: bool = False):
+def _check_keep_idx(keep_idx, B, device):
+    if (not isinstance(keep_idx, torch.Tensor) or keep_idx.dtype != torch.int32 or keep_idx.dim() != 2 or
+            keep_idx.shape[0] != B or keep_idx.shape[1] < 1 or not keep_idx.is_contiguous()):
+        raise ValueError(f'keep_idx must be a contiguous int32 [{B}, Lkeep >= 1] tensor of kept token numbers')
+    if keep_idx.device != device:
+        raise ValueError(f'keep_idx is on {keep_idx.device}, the video on {device}')
+
+
+def _forward_impl(m: VideoMAEBackbone, video: torch.Tensor, save: bool, token0_only: bool = False, keep_idx=None):
+    """keep_idx (int32 [B, Lkeep], ascending token numbers): masked-token encoding — the patch matrix and the position
+    rows are built for the kept tokens only and everything downstream runs with Lt := Lkeep (HF drops the masked
+    tokens right after the position add, modeling_videomae.py:109-122; a token's patch embedding depends on its own
+    patch only, so dropping before the projection computes the same rows)."""
     cfg = m.config
     W = m._weights()
     dt = W.dtype
@@ -294,12 +378,20 @@ def _forward_impl(m: VideoMAEBackbone, video: torch.Tensor, save: bool, token0_o
     pos = m.embeddings.position_embeddings
     if pos.shape[0] != Lt:
         raise ValueError(f'{Lt} tokens but the position table has {pos.shape[0]} rows (num_frames mismatch)')
-    M = B * Lt
+    if keep_idx is not None:
+        _check_keep_idx(keep_idx, B, video.device)
     scale = D ** -0.5
     video = video.contiguous().float()
-    patches = K.tubelet_im2col(video, tub, P, dt)
     pe = m.embeddings.patch_embeddings.projection
-    x = K.linear(patches, W['patch'], pe.bias, rowadd=pos, rowadd_mod=Lt)
+    if keep_idx is None:
+        M = B * Lt
+        patches = K.tubelet_im2col(video, tub, P, dt)
+        x = K.linear(patches, W['patch'], pe.bias, rowadd=pos, rowadd_mod=Lt)
+    else:
+        Lt = keep_idx.shape[1]
+        M = B * Lt
+        patches = K.tubelet_im2col_gather(video, tub, P, dt, keep_idx)
+        x = K.linear(patches, W['patch'], pe.bias, rowadd=K.gather_rows(pos, keep_idx), rowadd_mod=M)
     st = _Ctx()
     st.geom = (B, Lt, M, Hd, nh, D, scale)
     st.patches = patches if save else None
@@ -509,8 +601,9 @@ def _last_layer_token0_bwd(st, li, p, W, dx0, wgrad, ln_grads, sink, dev):
 
 class _BackboneFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, video, module, token0_only, *params):
-        x, st = _forward_impl(module, video, save=True, token0_only=token0_only)
+    def forward(ctx, video, module, token0_only, keep_idx, *params):
+        # keep_idx: integer kept-token list (or None) — a non-differentiable input; with it every size below is Lkeep's
+        x, st = _forward_impl(module, video, save=True, token0_only=token0_only, keep_idx=keep_idx)
         ctx.module, ctx.st, ctx.token0_only = module, st, token0_only
         ctx.params = params
         B, Lt, M, Hd = st.geom[:4]
@@ -541,23 +634,32 @@ class _BackboneFn(torch.autograd.Function):
         sink = getattr(m, '_grad_sink', None) or AutogradSink()
         _backward_impl(m, st, dx, sink, overlap_wgrad=getattr(m, "overlap_wgrad", _OVERLAP_WGRAD))
         ctx.st = None
-        out = [None, None, None]
+        out = [None, None, None, None]
         for p in ctx.params:
             out.append(sink.result(p) if p.requires_grad else None)
         return tuple(out)
 
 
-def run_backbone(m: VideoMAEBackbone, video: torch.Tensor, token0_only: bool) -> torch.Tensor:
+def run_backbone(m: VideoMAEBackbone, video: torch.Tensor, token0_only: bool, keep_idx=None) -> torch.Tensor:
     """Backbone forward (+ autograd node when gradients are needed).  Returns fp32 (B,Hd) token-0 features
-    (`last_hidden_state[:, 0]`, models.py:201) or the full fp32 last_hidden_state (B, L, Hd)."""
+    (`last_hidden_state[:, 0]`, models.py:201) or the full fp32 last_hidden_state (B, L, Hd).  keep_idx (int32
+    [B, Lkeep], see tube_keep_indices): encode the kept tokens only; L is then Lkeep and "token 0" the first kept
+    token."""
     params = list(m.parameters())
     if torch.is_grad_enabled() and any(p.requires_grad for p in params):
         if m.compute_dtype == 'fp16':
             raise RuntimeError("compute_dtype 'fp16' is the inference-only path (BASELINE config 5): run it under "
                                "torch.no_grad() / with frozen parameters, or use 'bf16' / 'fp32' for training")
-        return _BackboneFn.apply(video, m, token0_only, *params)
+        if keep_idx is not None and m.compute_dtype == 'bf16' and video.dim() == 5:
+            _check_keep_idx(keep_idx, video.shape[0], video.device)
+            rows = video.shape[0] * keep_idx.shape[1]
+            if rows % 8:
+                raise ValueError(f'bf16 training contracts the weight-gradient GEMMs over the B·Lkeep = {rows} kept '
+                                 f'token rows, which must be a multiple of 8 (tube_keep_indices(..., multiple=8)); '
+                                 f"use such a count or compute_dtype 'fp32'")
+        return _BackboneFn.apply(video, m, token0_only, keep_idx, *params)
     with torch.no_grad():
-        x, st = _forward_impl(m, video, save=False, token0_only=token0_only)
+        x, st = _forward_impl(m, video, save=False, token0_only=token0_only, keep_idx=keep_idx)
         B, Lt, M, Hd = st.geom[:4]
         if token0_only:
             out = torch.empty(B, Hd, dtype=torch.float32, device=x.device)

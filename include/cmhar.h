@@ -214,6 +214,20 @@ int cmhar_softmax_contrast_loss(int B, int D, const float* a, long lda, const fl
 int cmhar_tubelet_im2col(int out_dtype, int B, int T, int C, int H, int W, int tub, int P, const float* video,
                          void* out, hipStream_t stream);
 
+/* Masked-token encoding (replaces: `embeddings[~bool_masked_pos]`, modeling_videomae.py:109-122, taken before the
+ * patch projection instead of after it).  keep_idx: int32 [B, Lkeep] token numbers in [0, Lt), Lt = (T/tub)(H/P)(W/P),
+ * in the row order of cmhar_tubelet_im2col (t', h', w').  Output row b*Lkeep + j is exactly the row
+ * b*Lt + keep_idx[b][j] that cmhar_tubelet_im2col writes (same columns, same rounding); masked patches of the video are
+ * not read.  Every index is clamped into [0, Lt) before use.  Returns non-zero without launching when T % tub, H % P,
+ * W % P, P % 8, Lkeep < 1 or a pointer is null. */
+int cmhar_tubelet_im2col_gather(int out_dtype, int B, int T, int C, int H, int W, int tub, int P, const float* video,
+                                const int* keep_idx, int Lkeep, void* out, hipStream_t stream);
+
+/* out[m, 0:N] = table[clamp(idx[m], 0, rows_in_table - 1), 0:N], m < M (fp32; idx int32): the sin-cos position rows of
+ * the kept tokens (modeling_videomae.py:109-122) as an [M, N] matrix for the patch-embedding GEMM's rowadd. */
+int cmhar_gather_rows_f32(int M, int N, const float* table, long ld_table, int rows_in_table, const int* idx,
+                          float* out, long ld_out, hipStream_t stream);
+
 /* IMU PatchTST embedding + CLS + positional truncation (replaces: models.py:30-50, 108-123).
  * w, bias, dw, db: HOST arrays of C device pointers. */
 int cmhar_imu_embed_fwd(int B, int C, int L, int N, int P, int S, int D, int T, const float* x,
